@@ -21,7 +21,13 @@ Prints ONE JSON line on rank 0 (contract in the task description), including
   "roofline":     live HIP-event timing of the path's dominant m-sized kernel against the roofline
                   that bounds it (fp32 MFMA or HBM), with SURVEY's algorithmic flops/bytes and the
                   flops the kernel really executes
-  "cpu_baseline": the NumPy oracle (oracle/, the reference's op order) timed on this host's cores.
+  "cpu_baseline": the NumPy oracle (oracle/, the reference's op order) timed on this host's cores (--full).
+
+A plain run sets up, pre-rolls and warms up, times the K steps and prints the line.  --full adds
+every other figure: the cold first call, the compute_err=True rate, the class-level rate, the
+other transport at N > 1, NMFALS' settled / from-the-start rates and QP counts, cfg5's Gram-space
+loop and one-pass kernel, the CPU baseline and the full-size parity against the oracle.
+--dump-outputs DIR writes the factors the timed loop left behind (W, H; see dump_outputs()).
 """
 import argparse
 import json
@@ -321,6 +327,31 @@ def sharded_parity_nmf(ctx, dist, fac, m, n, k, lo, hi):
                        "||X_gpu - X_ref||_F / ||X_ref||_F" % (m, n, k, w.size)}
 
 
+DUMP_BYTES_MAX = 48 << 20       # --dump-outputs: W and H together stay under this
+
+
+def dump_outputs(ctx, dist, out_dir, m, lo, hi):
+    """--dump-outputs: the factors the timed loop left on the device, as a caller of factorize() receives them.  H (k x n,
+    replicated) whole, in float64 (SNMF keeps it in float64 on the device, the others widen exactly); W (m x k, rows sharded
+    over the ranks) in float32, whole when it fits in DUMP_BYTES_MAX, else the rows of a fixed sample: RandomState(0), sorted,
+    the same rows for any rank count.  Collective; rank 0 writes DIR/W.npy and DIR/H.npy."""
+    k, n = ctx.k, ctx.n
+    H = np.empty((k, n), dtype=np.float64)
+    ctx.get_h_into(H)
+    rows_max = max((DUMP_BYTES_MAX - H.nbytes) // (4 * k), 1)
+    rows = np.arange(m) if m <= rows_max else np.sort(np.random.RandomState(0).choice(m, rows_max, replace=False))
+    mine = rows[(rows >= lo) & (rows < hi)] - lo
+    Wl = ctx.get_w()
+    blocks = dist.gather_bytes(np.ascontiguousarray(Wl[mine]).tobytes(), tag="dumpW")
+    del Wl
+    if blocks is None:
+        return
+    W = np.frombuffer(b"".join(blocks), dtype=np.float32).reshape(len(rows), k)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "W.npy"), W)
+    np.save(os.path.join(out_dir, "H.npy"), H)
+
+
 def _visible_devices(timeout=180.0):
     """The number of GPUs a rank process will see, counted by a CHILD process (pmf_device_count): the launcher itself makes
     no HIP call (a process that has initialised the GPU must not be the parent that replaces / outlives the ranks)."""
@@ -431,6 +462,10 @@ def main():
                     help="disclosed device pre-conditioning: untimed iterations of the same loop for about this "
                          "many ms of device time BEFORE the W counted warm-up steps (the chip's clock/power "
                          "state needs more than 5 launches to settle on a fresh box); 0 disables")
+    ap.add_argument("--settle-iters", type=int, default=500,
+                    help="untimed iterations from the seeded W0 / H0 after the pre-roll, before the W warm-up steps: the clock "
+                         "drops during the upload of W0 / H0 (not NMFALS, whose timed steps start from the seeded state; none "
+                         "with --preroll-ms 0)")
     ap.add_argument("--fill", choices=["numpy", "device", "fast"], default="numpy",
                     help="numpy: BASELINE.md protocol; device: counter-based fill of dense inputs (fast start-up); "
                          "fast: cfg5 only, a Poisson/uniform CSR stand-in of the same density (seconds, not a minute)")
@@ -443,6 +478,12 @@ def main():
                     help="pmf_set_option(NAME, VALUE) on the bench context (A/B measurements of tuning knobs)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
                     help="--gpus N > 1 without a launcher: wall-clock limit (s) for the N rank processes this script starts")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (cold call, compute_err=True rate, "
+                         "class-level rate, other transport, NMFALS / cfg5 extras, CPU baseline, full-size parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the factors they computed as DIR/W.npy (float32; a fixed seeded "
+                         "sample of rows when W is large) and DIR/H.npy (float64)")
     ap.add_argument("--cpu-baseline-child", metavar="DIR", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -480,7 +521,8 @@ def main():
     data = "synthetic"
     nnz_local = 0
     host = {}                    # host copies for the class-level measurement (1 rank, numpy fill)
-    want_class = (w.size == 1 and not args.no_class_rate)
+    want_class = (args.full and w.size == 1 and not args.no_class_rate)
+    start = {}                   # the seeded W0 / H0 (numpy fill), restored before the warm-up
     if args.config == "cfg5":
         ip, ix, vv = gen_csr(m, n, 0.01, lo, hi, fast=(args.fill != "numpy"))
         nnz_local = int(vv.shape[0])
@@ -511,6 +553,7 @@ def main():
         H0 = np.random.random((k, n))
         ctx.set_w(W0)
         ctx.set_h(H0)
+        start["W0"], start["H0"] = W0, H0
         if want_class and "V" in host:
             host["W"], host["H"] = W0, H0
         if algo_name == "NMFALS":
@@ -520,13 +563,15 @@ def main():
     # ---- the COLD figure: the very first factorize(K) of this context on resident data -- no pre-roll, no
     # warm-up, the chip at whatever clock it idles at, one-time work of a first call included; printed as a top-level sibling
     # of the pre-rolled `value` so that both clock states are one glance apart ----
-    ctx.synchronize()
-    dist.barrier()
-    tc = time.perf_counter()
-    _, done_c, _ = ctx.factorize(args.steps, compute_err=False)
-    ctx.synchronize()
-    cold_dt = dist.allreduce_max(time.perf_counter() - tc)
-    cold_rate = done_c / cold_dt
+    cold_rate = None
+    if args.full:
+        ctx.synchronize()
+        dist.barrier()
+        tc = time.perf_counter()
+        _, done_c, _ = ctx.factorize(args.steps, compute_err=False)
+        ctx.synchronize()
+        cold_dt = dist.allreduce_max(time.perf_counter() - tc)
+        cold_rate = done_c / cold_dt
 
     # ---- disclosed pre-conditioning (untimed, reported as "preroll_ms" / "preroll_iters") ----
     preroll_iters, preroll_ms = 0, 0.0
@@ -540,16 +585,22 @@ def main():
         ctx.factorize(preroll_iters, compute_err=False)
         preroll_ms = ctx.last_loop_ms()
         preroll_iters += 4
-        if state_dependent and "W0" in host:
-            # BASELINE.md section 3 / SURVEY 8(d): warm-up and timed iterations start from the SEEDED W0 / H0.  The pre-roll
-            # only brings the chip to its clock; the factors go back to the seeded start, so `value` includes the expensive
-            # first iterations (every row QP still changing its active set) -- the settled rate is reported beside it.
-            ctx.set_w(host["W0"])
-            ctx.set_h(host["H0"])
-
-    elif state_dependent and "W0" in host:       # (no pre-roll: the cold call above still moved the factors)
-        ctx.set_w(host["W0"])
-        ctx.set_h(host["H0"])
+    # BASELINE.md section 3 / SURVEY 8(d): warm-up and timed iterations start from the SEEDED W0 / H0.  The pre-roll (and the
+    # cold call of --full) only bring the chip to its clock, for a number of iterations that depends on its timing; the factors
+    # go back to the seeded start, so the timed steps -- and what --dump-outputs writes -- depend on the arguments alone.
+    # NMFALS: `value` includes the expensive first iterations (every row QP still changing its active set) -- the settled rate
+    # is reported beside it (--full).  The other algorithms then run --settle-iters untimed iterations: the upload of W0 / H0
+    # is a pause long enough for the clock to drop (cfg4: the first 20 launches after it 0.67 ms, settled 0.60 ms).
+    if "W0" in start:
+        ctx.set_w(start["W0"])
+        ctx.set_h(start["H0"])
+    else:
+        ctx.fill_w_uniform(42, lo)
+        ctx.fill_h_uniform(43)
+    settle_iters = 0 if (state_dependent or args.preroll_ms <= 0) else args.settle_iters
+    if settle_iters > 0:
+        _, done, _ = ctx.factorize(settle_iters, compute_err=False)
+        assert done == settle_iters
 
     # ---- warm-up (untimed) ----
     if args.warmup > 0:
@@ -584,11 +635,13 @@ def main():
     first_ms = [round(float(x), 4) for x in all_ms[:5]]
     ctx.profile_enable(False)
     per_rank_kernel_ms = dist.allgather_float(stats["mean_ms"])        # every rank's shard kernel: a slow GPU shows
+    if args.dump_outputs:
+        dump_outputs(ctx, dist, args.dump_outputs, m, lo, hi)
     # ---- N > 1: the OTHER transport in the same run.  `value` above rode on the one-shot exchange when it
     # passed its self-test; the same K steps once more with the per-iteration sum carried by the transport behind it --
     # ncclAllReduce (RCCL) on a multi-GPU node, the host round trip where the ranks share a GPU (RCCL refuses that set-up) ----
     other_transport = None
-    if w.size > 1 and algo_name == "NMF":
+    if args.full and w.size > 1 and algo_name == "NMF":
         behind = ("host transport (TCP star through rank 0; the ranks share GPU 0 and RCCL refuses two ranks on one GPU) -- "
                   "NOT RCCL, a plumbing figure" if dist.transport() in ("host", "ipc") else "ncclAllReduce (RCCL)")
         if dist.LAST_SETUP.get("oneshot") == "passed":
@@ -614,7 +667,7 @@ def main():
                                "was carried by this transport" % dist.LAST_SETUP.get("oneshot")}
     # NMFALS: the rate once the active sets have settled (about 300 iterations from the seeded start), same K steps
     settled, qp_counts = None, None
-    if state_dependent:
+    if args.full and state_dependent:
         more = max(0, 300 - (args.warmup + args.steps))
         if more:
             ctx.factorize(more, compute_err=False)
@@ -648,7 +701,7 @@ def main():
     # secondary: the API-default compute_err=True rate (not the headline value; the reference has no
     # error on sparse data, nmf.py:109-112)
     rate_err = None
-    if args.config != "cfg5":
+    if args.full and args.config != "cfg5":
         ne = max(2, min(args.steps, 20))
         ctx.synchronize()
         dist.barrier()
@@ -662,7 +715,7 @@ def main():
     # NMFALS: `value` is the rate once the pre-roll has run (the active sets of most rows have settled: one solve per
     # row QP).  Beside it: the first iterations from the random start, where every row QP still changes its set.
     rate_from_start = None
-    if algo_name == "NMFALS" and "W0" in host:
+    if args.full and algo_name == "NMFALS" and "W0" in host:
         ctx.set_w(host["W0"])
         ctx.set_h(host["H0"])
         ns0 = max(2, min(args.steps, 10))
@@ -681,7 +734,7 @@ def main():
     # amortised rate for this K, taken apart into its fixed cost and its per-iteration cost, and COLD (fresh
     # V: the one-time C = V^T V inside the measured call) -- and round 1's one-pass CSR kernel.
     gram_loop, rate_pass_per_iter = None, None
-    if args.config == "cfg5" and args.snmf_gram == -1:
+    if args.full and args.config == "cfg5" and args.snmf_gram == -1:
         def timed(steps):
             ctx.synchronize()
             dist.barrier()
@@ -748,7 +801,7 @@ def main():
                 mdl._ctx.close()
         del mdl
     als_sample = None
-    if (algo_name == "NMFALS" and w.size == 1 and not args.no_cpu_baseline and "W0" in host and "V" in host
+    if (args.full and algo_name == "NMFALS" and w.size == 1 and not args.no_cpu_baseline and "W0" in host and "V" in host
             and not hasattr(host["V"], "tocsr")):
         # one iteration at FULL size from the seeded start, kept for the oracle (cpu_baseline times exactly these QPs)
         ctx.set_w(host["W0"]); ctx.set_h(host["H0"])
@@ -772,7 +825,7 @@ def main():
     # oracle on the host's cores AFTER every timed region (the other ranks wait in the barrier behind it: the rendezvous sockets
     # block without a time limit, and nothing is being measured any more); the sharded parity run follows on all ranks ----
     cb_multi, par_multi = None, None
-    if w.size > 1 and not args.no_cpu_baseline:
+    if args.full and w.size > 1 and not args.no_cpu_baseline:
         fac_m = None
         if w.rank == 0:
             cb_multi, fac_m = cpu_baseline_in_child(args.config, m, n, k)
@@ -815,8 +868,10 @@ def main():
             "n_gpus": w.size,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,                     # False: the figures that --full adds are absent or None
             "preroll_ms": preroll_ms,
             "preroll_iters": preroll_iters,
+            "settle_iters": settle_iters,
             "ms_per_step": dt / args.steps * 1e3,
             "cold_iters_per_sec": cold_rate,       # the first factorize(K) on resident data: no pre-roll, no warm-up (see preroll_ms)
             "rank_ms_per_step": [x / args.steps * 1e3 for x in rank_dt],
@@ -892,10 +947,12 @@ def main():
                 out["roofline"]["qp_counts"] = dict(qp_counts, w_half_steps=nl,
                                                     passes_per_wave_task=passes / float(max(tasks, 1)),
                                                     mean_largest_system=nssum / float(max(passes, 1)))
+            elif quad and not args.full:          # (the counts come from the counting pass of --full)
+                fma_flop, src = None, None
             else:                                 # lane-per-variable kernel: DESIGN.md 3.4, profiles/r02_pmc_summary.csv
                 fma_flop = 2.0 * 2.24e5 * qps * (k / 64.0) ** 3
                 src = "modelled: profiles/r02_pmc_summary.csv (k_nnqp, 2.24e5 FMA per QP at k = 64)"
-            if mean_s > 0:
+            if mean_s > 0 and fma_flop is not None:
                 out["roofline"].update(bound="valu_f64", achieved=fma_flop / mean_s / 1e12, peak=78.6, unit="TFLOP/s",
                                        frac=fma_flop / mean_s / 1e12 / 78.6, flops_per_launch=fma_flop,
                                        executed_flops_per_launch=fma_flop, executed_TFLOPs=fma_flop / mean_s / 1e12)
@@ -909,9 +966,12 @@ def main():
                                                               "peak_Ginstr_per_s": 1024 * 2.4 / 4.0,
                                                               "frac": valu_instr / mean_s / 1e9 / (1024 * 2.4 / 4.0),
                                                               "source": "profiles/r03_pmc_cfg3_nnqp_quad.txt (settled state); not counted in this run"}
-            out["roofline"]["note"] = ("float64 VALU kernel: `achieved` = executed FMA flop of the row QPs (live device counts) / live launch "
-                                       "time of the 16-slot-frame launch plus the 32-slot one behind it; the kernel is bound by the dependent "
-                                       "chains of its factorisations and triangular solves at two / three waves per SIMD, not by flops")
+            if fma_flop is not None:
+                out["roofline"]["note"] = ("float64 VALU kernel: `achieved` = executed FMA flop of the row QPs (live device counts) / live launch "
+                                           "time of the 16-slot-frame launch plus the 32-slot one behind it; the kernel is bound by the dependent "
+                                           "chains of its factorisations and triangular solves at two / three waves per SIMD, not by flops")
+            else:
+                out["roofline"]["note"] = "float64 VALU kernel: its executed flop come from the QP counts of --full"
         if args.config == "cfg5":
             out["config"]["nnz_local"] = nnz_local
             out["config"]["gram_space_loop_w_once_per_factorize"] = gram_loop
@@ -923,7 +983,7 @@ def main():
         if cb_multi is not None:
             out["cpu_baseline"] = cb_multi
             out["parity_full_size"] = par_multi
-        if w.size == 1 and not args.no_cpu_baseline:
+        if args.full and w.size == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args.config, m, n, k, sample=als_sample)
             fac = cb.pop("_oracle_factors", None)
             par = cb.pop("_parity", None)

@@ -34,7 +34,7 @@ def test_two_rank_bench_line_on_one_gpu():
     for attempt in range(5):        # the rendezvous port is picked, released and re-bound by the launcher: a rare race
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "2",
-               "--rows", "131072", "--fill", "device", "--debug-share-gpu", "--no-cpu-baseline", "--preroll-ms", "20"]
+               "--rows", "131072", "--fill", "device", "--debug-share-gpu", "--no-cpu-baseline", "--preroll-ms", "20", "--full"]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900,
                            env=dict(os.environ, OMP_NUM_THREADS="4"))
         if p.returncode == 0:
@@ -79,7 +79,7 @@ def test_bench_starts_its_own_ranks_without_a_launcher():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "2", "--rows", "131072",
-           "--preroll-ms", "20"]
+           "--preroll-ms", "20", "--full"]
     p = subprocess.run(cmd + ["--debug-share-gpu"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200, env=env)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [json.loads(l) for l in p.stdout.decode().splitlines() if l.startswith("{")]

@@ -12,7 +12,7 @@ declare -A ARGS=( [cfg4]="--steps 10 --warmup 2 --fill device" [cfg2]="--config 
 for c in $cfgs; do
   for pass in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
     name=$(echo $pass | cut -d' ' -f1)
-    rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $O/${c}_$name -- python3 $R/bench.py --gpus 1 ${ARGS[$c]} --no-cpu-baseline --preroll-ms 0 > $O/${c}_$name.log 2>&1
+    rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $O/${c}_$name -- python3 $R/bench.py --gpus 1 ${ARGS[$c]} --full --no-cpu-baseline --preroll-ms 0 > $O/${c}_$name.log 2>&1
   done
 done
 python3 $R/tools/pmc_summary.py $O $tag

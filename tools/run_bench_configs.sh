@@ -9,9 +9,9 @@ cd /tmp && export TMPDIR=/tmp
 declare -A ARGS=( [cfg4]="--steps 20 --warmup 5" [cfg2]="--config cfg2 --steps 200 --warmup 5" \
                   [cfg3]="--config cfg3 --steps 50 --warmup 3" [cfg5]="--config cfg5 --steps 20 --warmup 5" )
 for c in ${CONFIGS:-cfg4 cfg2 cfg3 cfg5}; do
-  python3 $R/bench.py --gpus 1 ${ARGS[$c]} > $O/$c.json 2> $O/$c.err
+  python3 $R/bench.py --gpus 1 ${ARGS[$c]} --full > $O/$c.json 2> $O/$c.err
   tail -c 400 $O/$c.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$c -- python3 $R/bench.py --gpus 1 ${ARGS[$c]} --no-cpu-baseline > $O/${c}_under_rocprof.json 2> $O/${c}_rocprof.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$c -- python3 $R/bench.py --gpus 1 ${ARGS[$c]} --full --no-cpu-baseline > $O/${c}_under_rocprof.json 2> $O/${c}_rocprof.err
   f=$(find $O/prof_$c -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp "$f" $O/${c}_kernel_stats.csv
   find $O/prof_$c -name "*kernel_trace.csv" -delete
