@@ -34,6 +34,8 @@
  *   pmf_rnmf_update_s     RNMF.update_s                pymf/rnmf.py:96-98   (algo 4, 'next' row)
  *   pmf_nndsvd_init       NNDSVD.update_w + SVD        pymf/nndsvd.py:78-106, pymf/svd.py:105-148
  *   pmf_stream_*          the data[:,:] reads of       pymf/nmf.py:123,129 for data that is not resident
+ *   pmf_cnmf_init         CNMF.init_h + Kmeans         pymf/cnmf.py:78-103, pymf/kmeans.py:64-87 (algo 5)
+ *   pmf_set/get_g_f64     self.G of CNMF               pymf/cnmf.py:95-100
  *
  * Every function returns PMF_OK (0) or a negative status and never throws;
  * pmf_last_error() gives a human-readable message for the last failure.
@@ -58,7 +60,7 @@ enum {
   PMF_ESINGULAR = -5 /* SNMF: H H^T is singular (the reference's np.linalg.inv raises LinAlgError, snmf.py:69) */
 };
 
-enum { PMF_ALGO_NMF = 0, PMF_ALGO_NMFALS = 1, PMF_ALGO_SNMF = 2, PMF_ALGO_BNMF = 3, PMF_ALGO_RNMF = 4 };
+enum { PMF_ALGO_NMF = 0, PMF_ALGO_NMFALS = 1, PMF_ALGO_SNMF = 2, PMF_ALGO_BNMF = 3, PMF_ALGO_RNMF = 4, PMF_ALGO_CNMF = 5 };
 
 /* pmf_factorize flags (the reference's factorize() keyword arguments, nmf.py:141-142) */
 enum { PMF_COMPUTE_W = 1u, PMF_COMPUTE_H = 2u, PMF_COMPUTE_ERR = 4u };
@@ -179,6 +181,24 @@ int pmf_stream_end(pmf_ctx* ctx, double* ferr, int32_t* needs_direct);
  * reference's 1e-8 cut (svd.py:130-131); fewer than num_bases is PMF_EINVAL (the reference raises
  * IndexError).  Row-sharded contexts sum the Gram matrix and the split norms over all ranks. */
 int pmf_nndsvd_init(pmf_ctx* ctx, int32_t* rank_found);
+
+/* CNMF (algo 5; pymf/cnmf.py, convex NMF: W = data G, H >= 0, G >= 0; dense data, n <= 4096, num_bases <= 128, num_bases <= n,
+ * one rank -- pmf_ctx_create returns PMF_EINVAL otherwise).  The whole loop runs in Gram space on C = V^T V (n x n, float64,
+ * formed once per V); G (n x k) and H are kept in float64 on the device.  With algo 5 the common entry points mean:
+ *   pmf_set_h_f64 / pmf_get_h_f64   the float64 H as it is (exact round trip)
+ *   pmf_factorize                   cnmf.py:156-187 under the PMF_COMPUTE_* flags and conv_eps; one call, no host round trip per
+ *                                   iteration while the error runs on the trace identity
+ *   pmf_frobenius                   ||data - W H||: W = V G by the trace identity (the direct residual below 1e-3 of ||V||^2), or
+ *                                   the direct residual with a W the caller uploaded (pmf_set_w_*) until a G step rebinds W
+ *   pmf_get_w_*                     V G for the current G (materialised once), or the caller's W
+ *   pmf_update_w / pmf_update_h     no-ops, as cnmf.py:70-76
+ * pmf_cnmf_init = CNMF.init_h: Kmeans(data, num_bases).factorize(niter=km_niter) in Gram space from the centres data[:, sel]
+ * (sel: num_bases sorted distinct sample indices -- what random.sample drew, kmeans.py:71-74), then H = onehot^T + 0.2 and,
+ * unless G has been set, G = (onehot + 0.01) / count (cnmf.py:88-100); W = V G unless W was set.  assigned_out (may be NULL):
+ * the n cluster indices.  pmf_set_g_f64 / pmf_get_g_f64: G as a host n x k row-major float64 array, exact round trip. */
+int pmf_cnmf_init(pmf_ctx* ctx, const int32_t* sel, int32_t km_niter, int32_t* assigned_out);
+int pmf_set_g_f64(pmf_ctx* ctx, const double* G);
+int pmf_get_g_f64(pmf_ctx* ctx, double* G);
 
 /* Device time (ms, HIP events on the library's stream) of the last pmf_factorize loop. */
 int pmf_last_loop_ms(pmf_ctx* ctx, double* ms);

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PMF_LIB") or os.path.join(_HERE, "csrc", "libpymf_hip.so")   # PMF_LIB: A/B builds
 
 PMF_OK, PMF_EINVAL, PMF_EHIP, PMF_ENCCL, PMF_ENOMEM, PMF_ESINGULAR = 0, -1, -2, -3, -4, -5
-ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF = 0, 1, 2, 3, 4
+ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF = 0, 1, 2, 3, 4, 5
 COMPUTE_W, COMPUTE_H, COMPUTE_ERR = 1, 2, 4
 STREAM_RESID = 8
 NCCL_ID_BYTES = 128
@@ -60,6 +60,9 @@ SYMBOLS = [
     ("pmf_rnmf_get_s_f32", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_rnmf_set_s_f32", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_nndsvd_init", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
+    ("pmf_cnmf_init", _c.c_int, [_ctx, _c.c_void_p, _c.c_int32, _c.c_void_p]),
+    ("pmf_set_g_f64", _c.c_int, [_ctx, _c.c_void_p]),
+    ("pmf_get_g_f64", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_stream_begin", _c.c_int, [_ctx, _c.c_uint32, _c.c_int64]),
     ("pmf_stream_tile", _c.c_int, [_ctx, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64]),
     ("pmf_stream_end", _c.c_int, [_ctx, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int32)]),
@@ -335,6 +338,30 @@ class Context(object):
         found = ctypes.c_int32(0)
         self._chk(self._lib.pmf_nndsvd_init(self._h, ctypes.byref(found)))
         return int(found.value)
+
+    def cnmf_init(self, sel, km_niter=10):
+        """CNMF.init_h on the device (pmf_cnmf_init): k-means from the samples `sel` (sorted), then H, G (unless set) and
+        W = V G (unless set).  Returns the cluster index of every sample."""
+        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        assert sel.shape == (self.k,), (sel.shape, self.k)
+        out = np.empty(self.n, dtype=np.int32)
+        self._chk(self._lib.pmf_cnmf_init(self._h, sel.ctypes.data, int(km_niter), out.ctypes.data))
+        return out
+
+    def set_g(self, G):
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        assert G.shape == (self.n, self.k), (G.shape, self.n, self.k)
+        self._chk(self._lib.pmf_set_g_f64(self._h, G.ctypes.data))
+
+    def get_g(self):
+        G = np.empty((self.n, self.k), dtype=np.float64)
+        self._chk(self._lib.pmf_get_g_f64(self._h, G.ctypes.data))
+        return G
+
+    def get_h64(self):
+        H = np.empty((self.k, self.n), dtype=np.float64)
+        self._chk(self._lib.pmf_get_h_f64(self._h, H.ctypes.data))
+        return H
 
     def last_loop_ms(self):
         ms = ctypes.c_double(0.0)

@@ -34,6 +34,7 @@
 #include "pmf_csr.h"
 #include "pmf_nndsvd.h"
 #include "pmf_topk.h"
+#include "pmf_cnmf.h"
 
 namespace {
 
@@ -171,6 +172,17 @@ struct pmf_ctx {
   bool vnorm_valid = false;
   bool vnorm_local_valid = false;   // dScal[6] = sum(V^2) over this rank's rows (formed behind the upload)
   double vnorm2 = 0.0;          // ||V||_F^2 over all ranks
+  // CNMF (pmf_cnmf.h; num_bases <= 128, H in dHd / dH): G^T [KP][np], the split products (neg(C) G)^T, (pos(C) G)^T and
+  // H neg(C), H pos(C) (the latter two also hold Z^T, (C Z)^T of the k-means initialisation), L_A = A^T G, L_B = B^T G,
+  // the error terms; k-means: assignment, member counts, squared distances, z^T C z, the selected samples
+  double *dGT = nullptr, *dCnA = nullptr, *dCnB = nullptr, *dCnHn = nullptr, *dCnHp = nullptr, *dCnLA = nullptr, *dCnLB = nullptr,
+         *dCnTT = nullptr, *dKmDmin = nullptr, *dKmZcz = nullptr;
+  int *dKmAsg = nullptr, *dKmCnt = nullptr, *dKmSel = nullptr;
+  bool have_g = false;          // G set (pmf_set_g_f64 / pmf_cnmf_init)
+  bool cn_ab_valid = false;     // dCnA / dCnB belong to the current G and C
+  bool cn_l_valid = false;      // dCnLA / dCnLB belong to the current G and C
+  bool cn_user_w = false;       // W was uploaded by the caller (not V G): the error is the direct residual with it
+  double cn_trc = 0.0;          // tr(C) of the current C
   double lamb_w = 0.0, lamb_h = 0.0;   // BNMF penalty weights (bnmf.py:84-85,118-119)
   // streamed V (pmf_stream_*): row tiles pass through two device buffers, V is never resident
   float* dTile[2] = {nullptr, nullptr};
@@ -681,7 +693,7 @@ int csr_ps(pmf_ctx* c) {   // slabs: S part by the dense W^T W kernel, P part by
 }
 
 // SNMF keeps H in float64 on the device (num_bases <= 128)
-static inline bool h_in_f64(const pmf_ctx* c) { return c->algo == PMF_ALGO_SNMF && c->nb == 1; }
+static inline bool h_in_f64(const pmf_ctx* c) { return (c->algo == PMF_ALGO_SNMF || c->algo == PMF_ALGO_CNMF) && c->nb == 1; }
 
 // dHd exists and agrees with dH: entries whose rounding is not the float32 H any more are replaced by the widened float32 value
 int ensure_hd(pmf_ctx* c) {
@@ -1760,6 +1772,11 @@ int materialize_w(pmf_ctx* c) {
     rc = csr_w(c);
     c->ps_valid = keep_ps;
   } else {
+    if (c->algo == PMF_ALGO_CNMF) {   // W = V G: the "M^T" operand is the float32 rounding of G^T
+      const int64_t E = (int64_t)c->KP * c->np;
+      hipLaunchKernelGGL(k_f64_to_f32, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c->stream, c->dGT, E, c->dMT);
+      HIPCHK(c, hipGetLastError());
+    }
     rc = rowgemm<EPI_STORE>(c, c->dV, c->np, c->np, c->dMT, c->np, nullptr, nullptr, c->dW);
   }
   stat_end(c, SITE_MATERIALIZE);
@@ -2291,6 +2308,238 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
   if (st.site != old_site) st.used = 0;
 }
 
+// ---- CNMF (pymf/cnmf.py) in Gram space: kernels in pmf_cnmf.h ------------------------------------------------------------
+// C = V^T V (ensure_vgram, float64, formed once per V) carries the whole loop: every product of cnmf.py:157-175 is one with
+// C, pos(C) or neg(C) and an n x k float64 matrix, or a k x k one.  W = V G is materialised when it is read (materialize_w).
+int cnmf_alloc(pmf_ctx* c) {
+  if (c->dGT) return PMF_OK;
+  const size_t kn = (size_t)c->KP * c->np, kk = (size_t)c->KP * c->KP;
+  for (double** p : {&c->dGT, &c->dCnA, &c->dCnB, &c->dCnHn, &c->dCnHp}) PMFCHK(dalloc(c, p, kn));
+  for (double** p : {&c->dCnLA, &c->dCnLB}) PMFCHK(dalloc(c, p, kk));
+  PMFCHK(dalloc(c, &c->dCnTT, 2));
+  PMFCHK(dalloc(c, &c->dKmDmin, (size_t)c->np));
+  PMFCHK(dalloc(c, &c->dKmZcz, (size_t)c->KP));
+  PMFCHK(dalloc(c, &c->dKmAsg, (size_t)c->np));
+  PMFCHK(dalloc(c, &c->dKmCnt, (size_t)c->KP));
+  PMFCHK(dalloc(c, &c->dKmSel, (size_t)c->KP));
+  if (!c->dHd) { PMFCHK(dalloc(c, &c->dHd, kn)); PMFCHK(dalloc(c, &c->dSd, kk)); c->hd_synced = false; }
+  return PMF_OK;
+}
+
+// C of the current V and its trace (one read back per new V)
+int cnmf_ensure_c(pmf_ctx* c) {
+  if (c->c_valid) return PMF_OK;
+  c->cn_ab_valid = c->cn_l_valid = false;
+  PMFCHK(ensure_vgram(c));
+  hipLaunchKernelGGL(k_cnmf_trace, dim3(1), dim3(1024), 0, c->stream, c->dC, c->np, c->dCnTT);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(&c->cn_trc, c->dCnTT, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PMF_OK;
+}
+
+// (neg(C) X, pos(C) X) for XT [KP][np]
+int cnmf_split(pmf_ctx* c, const double* XT, double* YnT, double* YpT) {
+  hipLaunchKernelGGL(k_cnmf_split_gemm, dim3((unsigned)(c->np / 16), (unsigned)(c->KP / 16)), dim3(64), 0, c->stream, XT, c->dC, c->np,
+                     YnT, YpT, c->stop_arg);
+  HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+// A = neg(C) G, B = pos(C) G (cnmf.py:159-160) and L_A = A^T G, L_B = B^T G of the current G
+int cnmf_ensure_ab(pmf_ctx* c) {
+  if (c->cn_ab_valid) return PMF_OK;
+  PMFCHK(cnmf_split(c, c->dGT, c->dCnA, c->dCnB));
+  c->cn_ab_valid = true;
+  c->cn_l_valid = false;
+  return PMF_OK;
+}
+int cnmf_ensure_l(pmf_ctx* c) {
+  PMFCHK(cnmf_ensure_ab(c));
+  if (c->cn_l_valid) return PMF_OK;
+  hipLaunchKernelGGL(k_cnmf_kxk2, dim3((unsigned)(c->KP / 16), (unsigned)(c->KP / 16), 2), dim3(64), 0, c->stream, c->dCnA, c->dCnB,
+                     c->dGT, c->np, c->KP, c->dCnLA, c->dCnLB, c->stop_arg);
+  HIPCHK(c, hipGetLastError());
+  c->cn_l_valid = true;
+  return PMF_OK;
+}
+
+// S = H H^T -> dSd (float64 H)
+int cnmf_gram_s(pmf_ctx* c) {
+  hipLaunchKernelGGL(k_gram<double>, dim3((unsigned)(c->KP / 16), (unsigned)(c->KP / 16)), dim3(256), 0, c->stream, c->dHd,
+                     (int64_t)c->np, c->np, c->KP, c->k, 0.0, c->dG, c->dSd);
+  HIPCHK(c, hipGetLastError());
+  c->g_valid = false;          // (dG now holds the float32 S: no consumer of the NMF Gram matrix runs on a CNMF context)
+  return PMF_OK;
+}
+
+int cnmf_mul_step(pmf_ctx* c, double* T, float* Tf, const double* P1, const double* P2, const double* L1, const double* L2,
+                  const double* X1, const double* X2) {
+  const dim3 grid((unsigned)(c->np / 16));
+#define PMF_CNMF_STEP(NT_) hipLaunchKernelGGL(k_cnmf_mul_step<NT_>, grid, dim3(64 * NT_), 0, c->stream, T, Tf, c->np, P1, P2, L1, L2, X1, X2, c->stop_arg)
+  switch (c->NT) {
+    case 1: PMF_CNMF_STEP(1); break;
+    case 2: PMF_CNMF_STEP(2); break;
+    case 4: PMF_CNMF_STEP(4); break;
+    default: PMF_CNMF_STEP(8); break;
+  }
+#undef PMF_CNMF_STEP
+  HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+// One iteration of cnmf.py:157-175.  s_fresh: dSd holds H H^T of the H the iteration ends with.
+int cnmf_iteration(pmf_ctx* c, bool cw, bool ch, bool* s_fresh) {
+  PMFCHK(cnmf_ensure_l(c));
+  *s_fresh = false;
+  if (ch) {                    // H <- H * sqrt((B + H^T G^T A)^T / ((A + H^T G^T B)^T + 1e-9))
+    PMFCHK(cnmf_mul_step(c, c->dHd, c->dH, c->dCnB, c->dCnA, c->dCnLA, c->dCnLB, c->dHd, c->dHd));
+    c->g_valid = false; c->num_valid = false; c->trace_ready = false;
+  }
+  if (cw) {                    // S = H H^T;  G <- G * sqrt((pos(C) H^T + A S) / (neg(C) H^T + B S + 1e-9));  W = V G
+    PMFCHK(cnmf_gram_s(c));
+    *s_fresh = true;
+    PMFCHK(cnmf_split(c, c->dHd, c->dCnHn, c->dCnHp));
+    PMFCHK(cnmf_mul_step(c, c->dGT, nullptr, c->dCnHp, c->dCnHn, c->dSd, c->dSd, c->dCnA, c->dCnB));
+    c->cn_ab_valid = c->cn_l_valid = false;
+    c->cn_user_w = false;      // cnmf.py:175 rebinds W to data G
+    c->w_implicit = true;
+    c->ps_valid = false;
+  }
+  return PMF_OK;
+}
+
+// The error terms of ||V - V G H|| into dCnTT (k_cnmf_err_terms): A, B, L_A, L_B of the current G -- which the next iteration's
+// H step reads as they are -- and S of the current H
+int cnmf_err_terms(pmf_ctx* c, bool s_fresh) {
+  PMFCHK(cnmf_ensure_l(c));
+  if (!s_fresh) PMFCHK(cnmf_gram_s(c));
+  hipLaunchKernelGGL(k_cnmf_err_terms, dim3(1), dim3(1024), 0, c->stream, c->dCnA, c->dCnB, c->dHd, (int64_t)c->KP * c->np,
+                     c->dCnLA, c->dCnLB, c->dSd, (int64_t)c->KP * c->KP, c->dCnTT, c->stop_arg);
+  HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+// ||data - W H|| (nmf.py:100-114) as CNMF.frobenius_norm sees it: W = V G through the trace identity
+//   ||V - V G H||^2 = tr(C) - 2 <C G, H^T> + <G^T C G, H H^T>,
+// the direct residual where that cancels (below 1e-3 of ||V||^2) or where the caller uploaded W.
+int cnmf_error(pmf_ctx* c, bool s_fresh, double* out) {
+  if (c->cn_user_w) return frobenius_direct(c, out);
+  PMFCHK(cnmf_err_terms(c, s_fresh));
+  double tt[2] = {0.0, 0.0};
+  HIPCHK(c, hipMemcpyAsync(tt, c->dCnTT, sizeof(tt), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const double e2 = c->cn_trc - 2.0 * tt[0] + tt[1];
+  if (!(e2 > 1e-3 * c->cn_trc)) return frobenius_direct(c, out);
+  *out = std::sqrt(e2);
+  return PMF_OK;
+}
+
+int cnmf_ready(pmf_ctx* c) {
+  if (!c->have_g) return fail(c, PMF_EINVAL, "G has not been set (pmf_set_g_f64 / pmf_cnmf_init)");
+  PMFCHK(cnmf_alloc(c));
+  PMFCHK(cnmf_ensure_c(c));
+  return ensure_hd(c);
+}
+
+// pmf_factorize for CNMF: the loop of cnmf.py:156-187.  With the error on and W = V G, chunks of iterations are enqueued back to
+// back and the error and the convergence test run on the device (k_conv_check, stop flag), as in the free-running loops of
+// pmf_factorize; near the cancellation threshold and with a caller's W the loop goes on iteration by iteration.
+int cnmf_factorize(pmf_ctx* c, int32_t niter, bool cw, bool ch, bool ce, double conv_eps, double* ferr, int32_t* iters_done,
+                   int32_t* converged_at) {
+  PMFCHK(cnmf_ready(c));
+  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+  constexpr int kChunk = 32;
+  int done = 0;
+  bool free_run = false;
+  for (int i = 0; i < niter; ++i) {                         // cnmf.py:121
+    if (c->abort_flag.load(std::memory_order_relaxed) != 0) break;
+    bool s_fresh = false;
+    if (free_run) {
+      const int chunk = std::min(kChunk, niter - i);
+      c->stop_arg = c->dStop;
+      int lrc = PMF_OK;
+      for (int j = 0; j < chunk && lrc == PMF_OK; ++j) {
+        lrc = cnmf_iteration(c, cw, ch, &s_fresh);
+        if (lrc == PMF_OK) lrc = cnmf_err_terms(c, s_fresh);
+        if (lrc == PMF_OK) {
+          hipLaunchKernelGGL(k_conv_check, dim3(1), dim3(64), 0, c->stream, c->dCnTT, 1, c->cn_trc, conv_eps, (double)c->n, i + j,
+                             c->dFerr, c->dStop);
+          if (hipGetLastError() != hipSuccess) lrc = fail(c, PMF_EHIP, "k_conv_check launch failed");
+        }
+      }
+      c->stop_arg = nullptr;
+      PMFCHK(lrc);
+      int hstop[2] = {0, -1};
+      HIPCHK(c, hipMemcpyAsync(hstop, c->dStop, sizeof(hstop), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(ferr + i, c->dFerr + i, (size_t)chunk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      if (hstop[0] == 0) {
+        done += chunk;
+        i += chunk - 1;
+        continue;
+      }
+      const int s_it = hstop[1];                           // iterations i .. s_it ran, the rest of the chunk were no-ops
+      done += s_it - i + 1;
+      if (hstop[0] == 1) {                                 // cnmf.py:184-187
+        if (converged_at) *converged_at = s_it;
+        break;
+      }
+      free_run = false;                                    // the identity cancels at s_it: its error directly, then on by hand
+      i = s_it;
+      PMFCHK(frobenius_direct(c, &ferr[i]));
+    } else {
+      PMFCHK(cnmf_iteration(c, cw, ch, &s_fresh));
+      ++done;
+      if (ce) PMFCHK(cnmf_error(c, s_fresh, &ferr[i]));    // cnmf.py:150
+    }
+    if (ce && i > 1) {                                     // nmf.py:134-139
+      const double derr = std::fabs(ferr[i] - ferr[i - 1]) / (double)c->n;
+      if (derr < conv_eps) {
+        if (converged_at) *converged_at = i;
+        break;
+      }
+    }
+    if (ce && !free_run && !c->cn_user_w && niter - (i + 1) >= 2 && ferr[i] * ferr[i] > 1e-2 * c->cn_trc) {
+      if (c->ferr_cap < niter) {
+        if (c->dFerr) { HIPCHK(c, hipFree(c->dFerr)); c->dFerr = nullptr; }
+        PMFCHK(dalloc(c, &c->dFerr, (size_t)niter));
+        c->ferr_cap = niter;
+      }
+      HIPCHK(c, hipMemcpyAsync(c->dFerr, ferr, (size_t)(i + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemsetAsync(c->dStop, 0, 2 * sizeof(int), c->stream));
+      free_run = true;
+    }
+  }
+  PMFCHK(materialize_w(c));    // W = V G once, the W the reference holds after the loop
+  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  c->last_loop_ms = ms;
+  if (ce) for (int q = done; q < niter; ++q) ferr[q] = 0.0;   // np.zeros(niter), cnmf.py:154
+  if (iters_done) *iters_done = done;
+  return PMF_OK;
+}
+
+// One pass of the Gram-space k-means: (C Z)^T = Z^T C, z^T C z, the assignment, the counts and the error of iteration `it`
+int kmeans_assign_pass(pmf_ctx* c, int it, double eps) {
+  const int np = c->np, KP = c->KP;
+  double *ZT = c->dCnHn, *CZT = c->dCnHp;
+  hipLaunchKernelGGL((k_dgemm_mfma<false>), dim3((unsigned)(np / 16), (unsigned)(KP / 16)), dim3(64), 0, c->stream, ZT, (int64_t)np,
+                     c->dC, (int64_t)np, np, CZT, (int64_t)np, (float*)nullptr, (int64_t)0, (const int*)c->dStop);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_kmeans_zcz, dim3((unsigned)c->k), dim3(256), 0, c->stream, ZT, CZT, np, c->dKmZcz, (const int*)c->dStop);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_kmeans_assign, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, c->dC, CZT, c->dKmZcz, (int)c->n, np,
+                     c->k, c->dKmAsg, c->dKmDmin, (const int*)c->dStop);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_kmeans_reduce, dim3(1), dim3(1024), 0, c->stream, c->dKmAsg, c->dKmDmin, (int)c->n, c->k, c->dKmCnt, c->dFerr, it,
+                     eps, c->dStop);
+  HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -2317,8 +2566,14 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                    int32_t rank, int32_t nranks, const void* nccl_id) {
   if (!out) return fail(nullptr, PMF_EINVAL, "out is NULL");
   *out = nullptr;
-  if (algo < 0 || algo > 4) return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF) or 4 (RNMF)");
+  if (algo < 0 || algo > 5) return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF) or 5 (CNMF)");
   if (m_local < 1 || n < 1 || k < 1) return fail(nullptr, PMF_EINVAL, "m, n, k must be >= 1");
+  if (algo == PMF_ALGO_CNMF) {  // C = V^T V is n x n float64 (128 MiB at the limit); the k x k factors on one float64 MFMA tile row
+    if (n > 4096) return fail(nullptr, PMF_EINVAL, "CNMF: n (samples) > 4096 is not supported by this build");
+    if (k > 128) return fail(nullptr, PMF_EINVAL, "CNMF: num_bases > 128 is not supported by this build");
+    if (k > n) return fail(nullptr, PMF_EINVAL, "CNMF: num_bases > n (the k-means initialisation samples num_bases columns)");
+    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "CNMF: one rank only in this build");
+  }
   // The reference has no limit on num_bases (nmf.py:116-120); the generic kernels beyond 128 bases have been checked against
   // the float64 oracles at 1 500, 2 304 and 2 432 bases (tests/sweeps/bigk_limit_probe.py, tests/test_gpu_bigk.py); beyond 2 432 (19 blocks of 128)
   // the 16-column block of H that k_nmf_h and k_trace_terms keep in LDS (64 bytes per basis) no longer fits the 160 KiB.  NMFALS /
@@ -2400,13 +2655,17 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
     c->ferr_cap = 4096;
     PMFCHK(dalloc(c, &c->dFerr, (size_t)c->ferr_cap));
     if (algo == PMF_ALGO_RNMF) PMFCHK(dalloc(c, &c->dD, (size_t)c->mp * c->np));
-    if (algo != PMF_ALGO_NMF) {
+    if (algo != PMF_ALGO_NMF && algo != PMF_ALGO_CNMF) {
       if (!c->dW1) PMFCHK(dalloc(c, &c->dW1, (size_t)std::max<int64_t>(c->mp, c->np) * c->KP));
       PMFCHK(dalloc(c, &c->dGinvT, (size_t)c->KP * c->KP));
     }
     if (algo == PMF_ALGO_SNMF) {
       PMFCHK(dalloc(c, &c->dMT, (size_t)c->KP * c->np));
       PMFCHK(dalloc(c, &c->dGinvD, (size_t)c->KP * c->KP));
+    }
+    if (algo == PMF_ALGO_CNMF) {
+      PMFCHK(dalloc(c, &c->dMT, (size_t)c->KP * c->np));   // float32 G^T: the operand of W = V G (materialize_w)
+      PMFCHK(cnmf_alloc(c));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
@@ -2427,6 +2686,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                                                                            : algo == PMF_ALGO_RNMF ? FUSED_RNMF
                                                                                                    : FUSED_NMF))
                                : std::string("tiled");
+  if (algo == PMF_ALGO_CNMF) c->path = "cnmf_gram";
   choose_stat_site(c, false);
   *out = c;
   return PMF_OK;
@@ -2454,6 +2714,9 @@ int pmf_ctx_destroy(pmf_ctx* c) {
   for (void* p : {(void*)c->dTile[0], (void*)c->dTile[1], (void*)c->dPSacc, (void*)c->dStAcc, (void*)c->dGpart,
                   (void*)c->dT1part, (void*)c->dTicket, (void*)c->dFerr, (void*)c->dStop, (void*)c->dWarm, (void*)c->dW2,
                   (void*)c->dMT, (void*)c->dGinvD, (void*)c->dC, (void*)c->dCslabs, (void*)c->dMTd, (void*)c->dPd, (void*)c->dInvA, (void*)c->dInvB, (void*)c->dQp, (void*)c->dSing, (void*)c->dBinv, (void*)c->dDefer, (void*)c->dNbig, (void*)c->dWsnap, (void*)c->dY0, (void*)c->dQstat, c->dStage, (void*)c->dGramPart, (void*)c->dGramTickets, (void*)c->dWideT, (void*)c->dWideN, (void*)c->dWideD, (void*)c->dHd, (void*)c->dSd, (void*)c->dHdSnap, (void*)c->dVmaxBits})
+    if (p) (void)hipFree(p);
+  for (void* p : {(void*)c->dGT, (void*)c->dCnA, (void*)c->dCnB, (void*)c->dCnHn, (void*)c->dCnHp, (void*)c->dCnLA, (void*)c->dCnLB,
+                  (void*)c->dCnTT, (void*)c->dKmDmin, (void*)c->dKmZcz, (void*)c->dKmAsg, (void*)c->dKmCnt, (void*)c->dKmSel})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : {c->ev_copied[0], c->ev_copied[1], c->ev_consumed[0], c->ev_consumed[1]})
     if (e) (void)hipEventDestroy(e);
@@ -2591,6 +2854,7 @@ int pmf_set_w_f32(pmf_ctx* c, const float* W) {
   PMFCHK(zero_padding(c, c->dW, c->KP, c->mp, c->m, c->k));
   PMFCHK(upload_padded(c, c->dW, c->KP, W, c->k, c->m, c->k));
   c->have_w = true; c->ps_valid = false; c->trace_ready = false; c->w_implicit = false;
+  c->cn_user_w = c->algo == PMF_ALGO_CNMF;   // (CNMF: the error is taken against this W until a G step rebinds it)
   return PMF_OK;
 }
 int pmf_set_w_f64(pmf_ctx* c, const double* W) {
@@ -2600,6 +2864,7 @@ int pmf_set_w_f64(pmf_ctx* c, const double* W) {
   PMFCHK(zero_padding(c, c->dW, c->KP, c->mp, c->m, c->k));
   PMFCHK(upload_rows<double>(c, c->dW, c->KP, W, c->k, c->m, c->k));
   c->have_w = true; c->ps_valid = false; c->trace_ready = false; c->w_implicit = false;
+  c->cn_user_w = c->algo == PMF_ALGO_CNMF;
   return PMF_OK;
 }
 int pmf_get_w_f64(pmf_ctx* c, double* W) {
@@ -2677,6 +2942,7 @@ int pmf_get_h_f32(pmf_ctx* c, float* H) {
 }
 
 int pmf_update_w(pmf_ctx* c) {
+  if (c && c->algo == PMF_ALGO_CNMF) return PMF_OK;   // cnmf.py:70-76: both hooks are no-ops (the updates live in factorize)
   PMFCHK(need(c, true, true, true));
   PMFCHK(do_update_w(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2684,6 +2950,7 @@ int pmf_update_w(pmf_ctx* c) {
   return check_singular(c);
 }
 int pmf_update_h(pmf_ctx* c) {
+  if (c && c->algo == PMF_ALGO_CNMF) return PMF_OK;
   PMFCHK(need(c, true, true, true));
   PMFCHK(do_update_h(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2692,6 +2959,10 @@ int pmf_update_h(pmf_ctx* c) {
 int pmf_frobenius(pmf_ctx* c, double* out) {
   PMFCHK(need(c, true, true, true));
   if (!out) return fail(c, PMF_EINVAL, "out is NULL");
+  if (c->algo == PMF_ALGO_CNMF) {
+    PMFCHK(cnmf_ready(c));
+    return cnmf_error(c, false, out);
+  }
   PMFCHK(do_frobenius(c, out));
   return ipc_check(c);
 }
@@ -2701,6 +2972,11 @@ int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, do
   PMFCHK(need(c, true, true, true));
   const bool cw = flags & PMF_COMPUTE_W, ch = flags & PMF_COMPUTE_H, ce = flags & PMF_COMPUTE_ERR;
   if (niter < 0 || (ce && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
+  if (c->algo == PMF_ALGO_CNMF) {
+    if (iters_done) *iters_done = 0;
+    if (converged_at) *converged_at = -1;
+    return cnmf_factorize(c, niter, cw, ch, ce, conv_eps, ferr, iters_done, converged_at);
+  }
   // every early (error) return below leaves no pipelined W = V M write in flight on the side stream: a caller that then
   // re-uploads W must not see the stale product land on top of it
   struct WPipeGuard {
@@ -2947,7 +3223,7 @@ int pmf_rnmf_set_s_f32(pmf_ctx* c, const float* S) {
 int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (c) c->hd_synced = false;
   if (!c) return PMF_EINVAL;
-  if (c->algo == PMF_ALGO_RNMF)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
+  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (!c->have_w || !c->have_h) return fail(c, PMF_EINVAL, "pmf_stream_begin: W and H must be set");
   if (max_tile_rows < 1) return fail(c, PMF_EINVAL, "pmf_stream_begin: max_tile_rows must be >= 1");
@@ -3135,8 +3411,91 @@ int pmf_stream_end(pmf_ctx* c, double* ferr, int32_t* needs_direct) {
 
 int pmf_nndsvd_init(pmf_ctx* c, int32_t* rank_found) {
   PMFCHK(need(c, true, false, false));
-  if (c->algo == PMF_ALGO_RNMF) return fail(c, PMF_EINVAL, "pmf_nndsvd_init: not for RNMF contexts");
+  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF) return fail(c, PMF_EINVAL, "pmf_nndsvd_init: not for RNMF / CNMF contexts");
   return nndsvd_init(c, rank_found);
+}
+
+int pmf_cnmf_init(pmf_ctx* c, const int32_t* sel, int32_t km_niter, int32_t* assigned_out) {
+  PMFCHK(need(c, true, false, false));
+  if (c->algo != PMF_ALGO_CNMF) return fail(c, PMF_EINVAL, "pmf_cnmf_init: CNMF contexts only");
+  if (c->v_csr) return fail(c, PMF_EINVAL, "CNMF: dense data only");
+  if (!sel || km_niter < 0) return fail(c, PMF_EINVAL, "pmf_cnmf_init: bad arguments");
+  for (int j = 0; j < c->k; ++j)
+    if (sel[j] < 0 || sel[j] >= c->n || (j > 0 && sel[j] <= sel[j - 1]))
+      return fail(c, PMF_EINVAL, "pmf_cnmf_init: sel must be num_bases sorted distinct sample indices");
+  PMFCHK(cnmf_alloc(c));
+  PMFCHK(cnmf_ensure_c(c));
+  if (c->ferr_cap < km_niter + 1) {
+    if (c->dFerr) { HIPCHK(c, hipFree(c->dFerr)); c->dFerr = nullptr; }
+    PMFCHK(dalloc(c, &c->dFerr, (size_t)km_niter + 1));
+    c->ferr_cap = km_niter + 1;
+  }
+  // Kmeans(data, num_bases).factorize(niter=km_niter) (cnmf.py:84-86): init_w = the selected samples, init_h = one assignment,
+  // then update_w, update_h and the error per iteration with the reference's early exit -- no host round trip in between
+  HIPCHK(c, hipMemcpyAsync(c->dKmSel, sel, (size_t)c->k * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->dStop, 0, 2 * sizeof(int), c->stream));
+  const int64_t E = (int64_t)c->KP * c->np;
+  const dim3 egrid((unsigned)std::min<int64_t>((E + 255) / 256, 2048));
+  hipLaunchKernelGGL(k_kmeans_seed, egrid, dim3(256), 0, c->stream, c->dCnHn, c->np, c->KP, c->k, (const int*)c->dKmSel);
+  HIPCHK(c, hipGetLastError());
+  PMFCHK(kmeans_assign_pass(c, -1, 1e-8));
+  for (int it = 0; it < km_niter; ++it) {
+    hipLaunchKernelGGL(k_kmeans_update, egrid, dim3(256), 0, c->stream, c->dCnHn, (int)c->n, c->np, c->k, (const int*)c->dKmAsg,
+                       (const int*)c->dKmCnt, (const int*)c->dStop);
+    HIPCHK(c, hipGetLastError());
+    PMFCHK(kmeans_assign_pass(c, it, 1e-8));                 // nmf.py:69 (_EPS), kmeans.py:76-81
+  }
+  // CNMF.init_h (cnmf.py:88-100): H from the assignment; G too unless the caller has set one
+  const bool with_g = !c->have_g;
+  hipLaunchKernelGGL(k_cnmf_init_hg, egrid, dim3(256), 0, c->stream, (const int*)c->dKmAsg, (const int*)c->dKmCnt, (int)c->n, c->np,
+                     c->KP, c->k, c->dHd, c->dH, c->dGT, 1, with_g ? 1 : 0);
+  HIPCHK(c, hipGetLastError());
+  if (assigned_out)
+    HIPCHK(c, hipMemcpyAsync(assigned_out, c->dKmAsg, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->have_h = true; c->g_valid = false; c->g_parts = 0; c->num_valid = false; c->trace_ready = false;
+  c->hd_synced = true; c->hd_force = false;                // (Hd and its rounding H written together)
+  if (with_g) {
+    c->have_g = true;
+    c->cn_ab_valid = c->cn_l_valid = false;
+    if (!c->cn_user_w) { c->have_w = true; c->w_implicit = true; }   // cnmf.py:102-103: W = data G unless W exists
+  }
+  return PMF_OK;
+}
+
+int pmf_set_g_f64(pmf_ctx* c, const double* G) {
+  if (!c || !G) return fail(c, PMF_EINVAL, "pmf_set_g_f64: bad arguments");
+  if (c->algo != PMF_ALGO_CNMF) return fail(c, PMF_EINVAL, "pmf_set_g_f64: CNMF contexts only");
+  HIPCHK(c, hipSetDevice(c->device));
+  PMFCHK(cnmf_alloc(c));
+  const size_t bytes = (size_t)c->n * c->k * sizeof(double);
+  PMFCHK(stage_reserve(c, bytes));
+  HIPCHK(c, hipMemcpyAsync(c->dStage, G, bytes, hipMemcpyHostToDevice, c->stream));
+  const int64_t E = (int64_t)c->KP * c->np;
+  hipLaunchKernelGGL(k_cnmf_g_to_gt, dim3((unsigned)std::min<int64_t>((E + 255) / 256, 2048)), dim3(256), 0, c->stream,
+                     reinterpret_cast<const double*>(c->dStage), (int)c->n, c->k, c->np, c->KP, c->dGT);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->have_g = true;
+  c->cn_ab_valid = c->cn_l_valid = false;
+  if (!c->cn_user_w) { PMFCHK(w_pipe_join(c)); c->have_w = true; c->w_implicit = true; }   // W = V G of the new G
+  return PMF_OK;
+}
+
+int pmf_get_g_f64(pmf_ctx* c, double* G) {
+  PMFCHK(need(c, false, false, false));
+  if (!G) return fail(c, PMF_EINVAL, "G is NULL");
+  if (c->algo != PMF_ALGO_CNMF) return fail(c, PMF_EINVAL, "pmf_get_g_f64: CNMF contexts only");
+  if (!c->have_g) return fail(c, PMF_EINVAL, "G has not been set (pmf_set_g_f64 / pmf_cnmf_init)");
+  const size_t bytes = (size_t)c->n * c->k * sizeof(double);
+  PMFCHK(stage_reserve(c, bytes));
+  const int64_t E = (int64_t)c->n * c->k;
+  hipLaunchKernelGGL(k_cnmf_gt_to_g, dim3((unsigned)std::min<int64_t>((E + 255) / 256, 2048)), dim3(256), 0, c->stream, c->dGT, (int)c->n,
+                     c->k, c->np, reinterpret_cast<double*>(c->dStage));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(G, c->dStage, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PMF_OK;
 }
 
 
