@@ -1,0 +1,372 @@
+// pmf_host_ctx.h -- the context (pmf_ctx), error plumbing (fail / HIPCHK / PMFCHK), device memory (dalloc / dfree / dgrow),
+// the event brackets of the profiled launch site, need() and the invalidation functions (v_replaced ... sums_dropped).
+// Host code of libpymf_hip.so: included by pmf_api.hip (the translation unit) in this order, nothing else includes it.
+#pragma once
+
+namespace {
+
+constexpr int PMF_HGRAM_MAX_WGS = 64;
+
+std::string g_create_error;
+
+// Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
+// m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS };
+
+struct KernelStat {
+  std::string name = "none";
+  int site = SITE_NONE;
+  double flops = 0.0, bytes = 0.0, exec_flops = 0.0;
+  std::vector<hipEvent_t> ev;   // pairs
+  size_t used = 0;              // events recorded since reset
+  int every = 1;                // pmf_set_option("profile_every", N): only every N-th launch of the site carries events -- a pair costs
+                                // the loop ~5 us (the queue processes two more packets and the dispatch's completion signal): 8 % of a
+                                // 60 us iteration when every launch is timed (tools/loop_probe.py, profiles/r05_experiments.md)
+  int64_t seen = 0;             // launches of the site since reset
+  bool open = false;            // stat_begin recorded, stat_end to follow
+};
+
+}  // namespace
+
+struct pmf_ctx {
+  int algo = 0;
+  int64_t m = 0, n = 0;
+  int k = 0, device = 0, rank = 0, nranks = 1;
+  int nb = 1;                   // > 1: num_bases > 128 (NMF): KP = 128 nb, bases handled in blocks of 128
+  std::vector<void*> owned;     // every device buffer of the context (dalloc / dalloc_raw): what dfree and pmf_ctx_destroy release
+  float* dW2 = nullptr;         // ... Den = W (H H^T), [mp][KP] (dW1 holds Num = V H^T)
+  float* dWideT = nullptr;      // chunk result of a product over more than PMF_WIDE_K columns
+  int64_t wide_cap = 0;
+  float *dWideN = nullptr, *dWideD = nullptr;   // ... Num and Den of the W rules there (wide_update_w_rows)
+  int64_t wide_nd_cap = 0;
+  int64_t mp = 0;
+  int np = 0, KP = 0, NT = 0;
+  hipStream_t stream = nullptr;
+  ncclComm_t comm = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  float *dV = nullptr, *dW = nullptr, *dH = nullptr, *dG = nullptr, *dPS = nullptr;
+  float *dSlab = nullptr, *dW1 = nullptr, *dGinvT = nullptr;
+  float* dMT = nullptr;         // SNMF: M^T = inv(H H^T) H, [KP][np] (k_snmf_mt)
+  double* dGinvD = nullptr;     // SNMF: inv(H H^T) in float64, [KP][KP]
+  // Gram-space SNMF loop (snmf_gram_iteration): C = V^T V over all ranks' rows, and the float64 M^T, P
+  double *dC = nullptr, *dMTd = nullptr, *dPd = nullptr;
+  // SNMF (num_bases <= 128): H in float64 on the device (pmf_inv.h, round 6) -- dH is its float32 rounding.  hd_synced: k_hd_sync
+  // has compared the two in THIS API call (need() clears it); ps_f64: (P | S) of the Gram-space iteration at hand are in dPd / dSd
+  double *dHd = nullptr, *dSd = nullptr, *dHdSnap = nullptr;
+  bool hd_synced = false, hd_force = false, ps_f64 = false;   // hd_force: H was replaced through a float32 entry point.  hd_synced, hd_force <- H
+  bool psd_fresh = false;      // dPd / dSd are the float64 (P | S) of the CURRENT W (set by a Gram-space iteration, for the error behind it; every API entry clears it: need())
+  double* dCslabs = nullptr;    // k_csr_gram: per-workgroup images of C's upper triangle (two 64-bit fixed-point limbs per entry)
+  unsigned* dVmaxBits = nullptr; // ... and the bit pattern of the largest |v| (the limbs' grids)
+  bool c_valid = false;         // dC holds the all-rank V^T V of the current V.  <- V, the transport of the cross-rank sums
+  int opt_snmf_gram = -1;       // pmf_set_option("snmf_gram"): -1 auto, 0 never, 1 whenever possible, 2 = 1 + W written in every iteration
+  bool w_implicit = false;      // the loop ran in Gram space: dW is stale, W = V M with the M at hand (materialize_w).  <- W (CNMF: set by a new G)
+  // snmf_gram = 2 on CSR data: W = V M of iteration i is written on a stream of its own BESIDE the k x n sized kernels of
+  // iteration i + 1 (they never read W); M is double buffered (dW1, dW1 + np KP) and the write launch leaves a few
+  // workgroup slots free so that the small kernels can be placed while it runs (w_pipe_* below, materialize_w)
+  hipStream_t w_stream = nullptr;
+  hipEvent_t ev_mt[2] = {nullptr, nullptr}, ev_w[2] = {nullptr, nullptr};
+  bool ev_w_pending[2] = {false, false};
+  int64_t w_pipe_it = 0;        // writes enqueued so far: buffer parity
+  int opt_w_pipe = 32;          // pmf_set_option("snmf_w_pipe"): workgroup slots the write launch leaves free; 0 = in stream order
+  float* dD = nullptr;          // RNMF: D = S - V (rnmf.py:102,111), [mp][np]
+  bool s_valid = false;         // RNMF: D has been formed (update_s ran)
+  double rnmf_err2 = -1.0;      // RNMF: sum((V - W H)^2) from the last update_s (all ranks)
+  double *dGd = nullptr, *dPart = nullptr, *dScal = nullptr;
+  double* dGramPart = nullptr;  // k_gram_splitk: per-slice partial Gram matrices, [8][KP][KP]
+  unsigned* dGramTickets = nullptr;   // k_gram_splitk: one per tile
+  float* dGpart = nullptr;      // k_nmf_h_gram: per-workgroup partial G, [PMF_HGRAM_MAX_WGS][KP][KP]
+  float* dHsnap = nullptr;      // pmf_snapshot_h: H, then G, then the partial Gs
+  bool hsnap_valid = false, hsnap_g_valid = false;
+  int hsnap_g_parts = 0;
+  double* dT1part = nullptr;    // ... and partial <P, H_new>
+  unsigned* dTicket = nullptr;  // ... arrival counter (the kernel resets it)
+  // free-running pmf_factorize loop: device-side error history and stop flag
+  double* dFerr = nullptr; int64_t ferr_cap = 0;
+  int* dStop = nullptr;         // [0] 0 run / 1 converged / 2 identity cancels, [1] iteration
+  int* dWarm = nullptr;         // k_nnqp: warm start allowed (k_spd_unique)
+  const int* stop_arg = nullptr;   // what the loop kernels get: dStop while free-running, else NULL
+  // free-running loop: the error / convergence test of iteration conv_iter (>= 0) is still to be evaluated, from
+  // conv_ntt pairs of trace terms at conv_tt; the next one-pass launch does it in its prologue (FusedCtl)
+  int conv_iter = -1, conv_ntt = 0;
+  const double* conv_tt = nullptr;
+  double conv_eps = 0.0;
+  // CSR V (SNMF sparse path)
+  int64_t* dIndptr = nullptr; int32_t* dIndices = nullptr; float* dVals = nullptr; int64_t nnz = 0;
+  bool v_csr = false;
+  bool csr_dense = false;       // CSR data with num_bases > 128: a dense image in dV serves the data paths (no CSR kernel at that width)
+  int* dSing = nullptr;         // SNMF: raised by the inverse kernels when H H^T has a zero pivot (check_singular)
+  double* dQp = nullptr;        // k_nnqp_big (NMFALS, num_bases > 64): per-workgroup inverse images
+  double* dBinv = nullptr;      // k_nnqp_quad: B = inv(HA), [KP][KP] float64
+  int* dDefer = nullptr;        // k_nnqp_quad<16>: problems left to the 32-slot frame
+  int64_t defer_cap = 0;
+  int* dNbig = nullptr;         // [2 sites][3 + 2]: rotating counters of k_nnqp_quad (QuadCtl: nbig x 3, dcount x 2)
+  int64_t quad_calls[2] = {0, 0};
+  unsigned long long* dQstat = nullptr;   // k_nnqp_quad, W half steps: [2 frames][4] running totals (pmf_nnqp_counters)
+  double* dY0 = nullptr;        // k_nnqp_wave: inv(HA) f of every problem of a half step
+  int64_t y0_cap = 0;
+  int opt_nnqp_wave = 1;        // pmf_set_option("nnqp_wave"): 64 < num_bases <= 128 on the wave-per-problem block-pivoting kernel
+  int opt_nnqp_frame16 = 1;     // pmf_set_option("nnqp_frame16"): the 16-slot frame first (three waves per SIMD)
+  int opt_nnqp_count = 0;       // pmf_set_option("nnqp_count"): the counting instantiations of k_nnqp_quad (pmf_nnqp_counters)
+  void* dStage = nullptr;       // staging area of the host <-> device transport (upload_rows / download_rows)
+  size_t stage_cap = 0;
+  float* dWsnap = nullptr;      // pmf_snapshot_w: the W before a step that may fail
+  bool wsnap_valid = false;
+  int opt_nndsvd_topk = -1;     // pmf_set_option("nndsvd_topk"): -1 by size, 1 the filtered subspace iteration, 0 full Jacobi
+  int nndsvd_products = 0;      // products with the Gram matrix the last top-k solve took
+  int opt_colgemm_stream = 1;   // pmf_set_option("colgemm_stream"): W^T V partials on k_colgemm_stream where it applies
+  int opt_resid_resident = 1;   // residual pass with H resident in LDS (k_resid_res) where it fits
+  int resid_parts = 0;          // float64 partials the last residual pass left in dPart
+  int64_t dpart_cap = 0;        // doubles dPart holds
+  int opt_rowgemm_stream = 1;   // pmf_set_option("rowgemm_stream"): plain products with a long contraction on k_rowgemm_stream
+  int opt_nnqp_quad = 1;        // pmf_set_option("nnqp_quad"): num_bases <= 64 on the sixteen-lanes-per-problem kernel
+  double *dInvA = nullptr, *dInvB = nullptr;   // k_inverse_spd_big: the two images of the elimination, [KP][KP]
+  int nchunks = 0, rows_per_chunk = 0;
+  int fused_wgs = 0;            // >0: fused one-pass kernel available for this shape
+  int fused_wgs_hidden = 0;     // pmf_set_option("force_tiled", 1) parks fused_wgs / fused8 here: every path then takes the
+  bool fused8_hidden = false;   // any-shape two-pass kernels (k_rowgemm / k_colgemm) -- test and measurement aid
+  std::string path_hidden;
+  bool fused8 = false;          // ... and it is the cooperative form (pmf_coop.h: 64 < k <= 128, or k <= 64 with n > 256)
+  int coop_bt = 0, coop_rb = 0; // its base tiles per wave / row blocks per tile
+  bool have_v = false, have_w = false, have_h = false, g_valid = false;   // g_valid: dG = H H^T.  g_valid, g_parts <- H
+  int g_parts = 0;              // > 0 (with g_valid): G = sum of that many partials in dGpart, dG is stale
+  int trace_parts = 0;          // > 0 (with trace_ready): the trace terms are that many pairs in dT1part
+  bool gram_partial_ok = false; // pmf_factorize: the next consumer of G is the fused kernel
+  bool want_hess = false, gd_is_s = false;   // NMFALS H half step: the reduce writes dGd = W^T W itself (reduce_slabs)
+  bool ps_valid = false;        // dPS = (W^T V | W^T W) of the CURRENT W, summed over all ranks.  <- V (RNMF: D), W, the transport
+  bool num_valid = false;       // dW1 holds Num = V H^T of the current V, H (fixed-H loops, NMF).  <- V, H; W too: dW1 is also the W steps' scratch
+  bool fixed_h_loop = false;    // pmf_factorize running compute_w without compute_h for > 1 iteration
+  bool want_trace = false;      // pmf_factorize with PMF_COMPUTE_ERR: let the H-step kernel emit the trace terms
+  bool trace_ready = false;     // dScal[2..3] already hold <P,H>, <S,HH^T> for the current W, H.  <- V, W, H, the transport (read with ps_valid only)
+  bool vnorm_valid = false;     // vnorm2 is current.  <- V, the transport
+  bool vnorm_local_valid = false;   // dScal[6] = sum(V^2) over this rank's rows (formed behind the upload).  <- V
+  double vnorm2 = 0.0;          // ||V||_F^2 over all ranks
+  // CNMF (pmf_cnmf.h; num_bases <= 128, H in dHd / dH): G^T [KP][np], the split products (neg(C) G)^T, (pos(C) G)^T and
+  // H neg(C), H pos(C) (the latter two also hold Z^T, (C Z)^T of the k-means initialisation), L_A = A^T G, L_B = B^T G,
+  // the error terms; k-means: assignment, member counts, squared distances, z^T C z, the selected samples
+  double *dGT = nullptr, *dCnA = nullptr, *dCnB = nullptr, *dCnHn = nullptr, *dCnHp = nullptr, *dCnLA = nullptr, *dCnLB = nullptr,
+         *dCnTT = nullptr, *dKmDmin = nullptr, *dKmZcz = nullptr;
+  int *dKmAsg = nullptr, *dKmCnt = nullptr, *dKmSel = nullptr;
+  bool have_g = false;          // G set (pmf_set_g_f64 / pmf_cnmf_init)
+  bool cn_ab_valid = false;     // dCnA / dCnB belong to the current G and C.  <- G, V (through c_valid: cnmf_ensure_c)
+  bool cn_l_valid = false;      // dCnLA / dCnLB belong to the current G and C.  <- G, V (as above)
+  bool cn_user_w = false;       // W was uploaded by the caller (not V G): the error is the direct residual with it.  <- W from the caller
+  double cn_trc = 0.0;          // tr(C) of the current C
+  double lamb_w = 0.0, lamb_h = 0.0;   // BNMF penalty weights (bnmf.py:84-85,118-119)
+  // streamed V (pmf_stream_*): row tiles pass through two device buffers, V is never resident
+  float* dTile[2] = {nullptr, nullptr};
+  int64_t tile_cap = 0;                      // rows per tile buffer (multiple of 64)
+  hipStream_t copy_stream = nullptr;
+  hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_consumed[2] = {nullptr, nullptr};
+  double* dPSacc = nullptr;                  // float64 (P | S) accumulated over the tiles of a pass
+  double* dStAcc = nullptr;                  // [0] sum v^2, [1] sum (v - (W H))^2 over the tiles
+  bool st_active = false, st_vnorm_pending = false;
+  uint32_t st_flags = 0;
+  int64_t st_rows_seen = 0;
+  int st_tiles = 0;
+  // one-shot all-reduce over IPC-mapped receive areas (pmf_ipc.h): payloads <= PMF_IPC_MAX_BYTES
+  IpcPeers ipc{};                            // ipc.nranks > 1: ready
+  bool ipc_exported = false;
+  unsigned long long ipc_wait_ticks = PMF_IPC_WAIT_TICKS;
+  int ipc_nranks_ready = 0;                  // ranks mapped by pmf_ipc_import (ipc.nranks = 0 while the path is switched off)
+  int ipc_export_nranks = 0;                 // the rank count pmf_ipc_export sized the receive area for
+  float *dIpcTestA = nullptr, *dIpcTestB = nullptr;   // pmf_ipc_selftest's payloads, allocated by pmf_ipc_export (no allocation -- nothing
+                                                      // that can fail locally -- between the self-test's collectives)
+  unsigned ipc_seq = 0;
+  std::atomic<int> abort_flag{0};            // pmf_abort: another host thread asks the running pmf_factorize loop to return early
+  // the folded exchange (round 5): inside pmf_factorize's one-pass loop the push rides on k_reduce_slabs_tiles and the wait +
+  // rank-ordered sum on k_nmf_h_gram's prologue -- no launch for the exchange (pmf_set_option("fold_exchange", 0): the
+  // k_ipc_allreduce launch of round 4 instead)
+  int opt_fold = 1;
+  bool fold_loop = false;                    // set by nmf_fused_iteration around its two launches
+  unsigned fold_seq = 0;                     // != 0: k_reduce_slabs_tiles has pushed exchange fold_seq, the next k_nmf_h_gram consumes it
+  int fold_flags = 0;                        // tiles (= flags) of that push
+  unsigned long long* dIpcWait = nullptr;    // [2]: ticks of the 100 MHz counter the consumer spent waiting, exchanges counted
+  int64_t fold_calls = 0;
+  int* dIpcErr = nullptr;
+  int64_t coll_seen = 0;
+  int64_t ipc_calls = 0, rccl_calls = 0, host_calls = 0;   // which transport the cross-rank sums took (pmf_collective_name)
+  pmf_host_allreduce_fn host_ar = nullptr;   // host transport for the cross-rank sums (pmf_set_host_allreduce)
+  void* host_ar_user = nullptr;
+  std::vector<unsigned char> ar_buf;
+  bool profile = false;
+  std::vector<hipEvent_t> coll_ev;           // event pairs around the per-iteration collective (allreduce_ps)
+  size_t coll_used = 0;
+  bool host_ar_only() const { return host_ar != nullptr && ipc.nranks <= 1 && comm == nullptr; }   // (blocking host round trips: nothing to time on the stream)
+  double last_loop_ms = 0.0;
+  KernelStat stat;
+  std::string err;
+  std::string path;
+};
+
+namespace {
+
+int fail(pmf_ctx* c, int code, const std::string& msg) {
+  if (c) c->err = msg; else g_create_error = msg;
+  return code;
+}
+
+#define HIPCHK(c, expr)                                                                   \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess)                                                                 \
+      return fail((c), e_ == hipErrorOutOfMemory ? PMF_ENOMEM : PMF_EHIP,                 \
+                  std::string(#expr) + ": " + hipGetErrorString(e_));                     \
+  } while (0)
+
+#define NCCLCHK(c, expr)                                                                  \
+  do {                                                                                    \
+    ncclResult_t r_ = (expr);                                                             \
+    if (r_ != ncclSuccess)                                                                \
+      return fail((c), PMF_ENCCL, std::string(#expr) + ": " + ncclGetErrorString(r_));    \
+  } while (0)
+
+#define PMFCHK(expr)                 \
+  do {                               \
+    int rc_ = (expr);                \
+    if (rc_ != PMF_OK) return rc_;   \
+  } while (0)
+
+int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+// defined further down the include order
+bool multi_rank(const pmf_ctx* c);
+int csr_ps(pmf_ctx* c);
+int csr_w(pmf_ctx* c, hipStream_t stream, const float* Mbuf, int reserve);
+int materialize_w(pmf_ctx* c);
+int nmf_fused_pass(pmf_ctx* c);
+int snmf_fused_pass(pmf_ctx* c);
+int snmf_inverse(pmf_ctx* c);
+int ensure_ps(pmf_ctx* c);
+
+// ---- device memory: every buffer of a context is allocated, grown and released here ----------
+// (the IPC receive area alone lives outside c->owned: it is allocated for export and peers hold handles to it)
+// `bytes` of device memory as hipMalloc leaves them: nothing on the stream
+int dalloc_raw(pmf_ctx* c, void** p, size_t bytes) {
+  void* q = nullptr;
+  HIPCHK(c, hipMalloc(&q, bytes));
+  if (q) c->owned.push_back(q);
+  *p = q;
+  return PMF_OK;
+}
+template <typename T>
+int dalloc_raw(pmf_ctx* c, T** p, size_t count) { return dalloc_raw(c, reinterpret_cast<void**>(p), count * sizeof(T)); }
+
+// `count` elements, zero filled in stream order
+template <typename T>
+int dalloc(pmf_ctx* c, T** p, size_t count) {
+  PMFCHK(dalloc_raw(c, p, std::max<size_t>(count, 1)));
+  HIPCHK(c, hipMemsetAsync(*p, 0, std::max<size_t>(count, 1) * sizeof(T), c->stream));
+  return PMF_OK;
+}
+
+// (hipFree waits for the device; a site whose buffer may still be read by work in flight synchronizes its stream first)
+template <typename T>
+int dfree(pmf_ctx* c, T** p) {
+  if (!*p) return PMF_OK;
+  void* q = (void*)*p;
+  *p = nullptr;
+  c->owned.erase(std::remove(c->owned.begin(), c->owned.end(), q), c->owned.end());
+  HIPCHK(c, hipFree(q));
+  return PMF_OK;
+}
+
+// a buffer that has become too small: released, then `count` zero filled elements
+template <typename T>
+int dgrow(pmf_ctx* c, T** p, size_t count) {
+  PMFCHK(dfree(c, p));
+  return dalloc(c, p, count);
+}
+// ... with a capacity field of its own: `*cap` x `per` elements held, `count` x `per` wanted; sync: work in flight may read the old one
+template <typename T>
+int dgrow(pmf_ctx* c, T** p, int64_t* cap, int64_t count, size_t per = 1, bool sync = false) {
+  if (*cap >= count) return PMF_OK;
+  if (sync && *p) HIPCHK(c, hipStreamSynchronize(c->stream));
+  *cap = 0;
+  PMFCHK(dgrow(c, p, (size_t)count * per));
+  *cap = count;
+  return PMF_OK;
+}
+
+// CSR kernels serve the data paths (SNMF, num_bases <= 128); wider contexts keep a dense image of the CSR rows
+static inline bool use_csr(const pmf_ctx* c) { return c->v_csr && !c->csr_dense; }
+
+int ensure_dv(pmf_ctx* c) {
+  if (c->dV) return PMF_OK;
+  return dalloc(c, &c->dV, (size_t)c->mp * c->np);
+}
+
+// ---- profiling of the dominant kernel -------------------------------------------------
+void stat_begin(pmf_ctx* c, int site) {
+  if (!c->profile || c->stat.site != site) return;
+  KernelStat& s = c->stat;
+  s.open = false;
+  if (s.seen++ % s.every != 0) return;
+  if (s.used + 2 > s.ev.size()) {
+    for (int q = 0; q < 2; ++q) {
+      hipEvent_t e;
+      if (hipEventCreate(&e) != hipSuccess) return;
+      s.ev.push_back(e);
+    }
+  }
+  (void)hipEventRecord(s.ev[s.used], c->stream);   // profiling aid: a failed record only loses a sample
+  s.open = true;
+}
+// The next pair of events of site `site`, to be attached to a dispatch (hipExtLaunchKernelGGL); nullptr when not profiling.
+void stat_pair(pmf_ctx* c, int site, hipEvent_t* e0, hipEvent_t* e1) {
+  *e0 = *e1 = nullptr;
+  if (!c->profile || c->stat.site != site) return;
+  KernelStat& s = c->stat;
+  if (s.seen++ % s.every != 0) return;
+  if (s.used + 2 > s.ev.size()) {
+    for (int q = 0; q < 2; ++q) {
+      hipEvent_t e;
+      if (hipEventCreate(&e) != hipSuccess) return;
+      s.ev.push_back(e);
+    }
+  }
+  *e0 = s.ev[s.used]; *e1 = s.ev[s.used + 1];
+  s.used += 2;
+}
+void stat_end(pmf_ctx* c, int site) {
+  if (!c->profile || c->stat.site != site) return;
+  KernelStat& s = c->stat;
+  if (!s.open || s.used + 2 > s.ev.size()) return;
+  s.open = false;
+  (void)hipEventRecord(s.ev[s.used + 1], c->stream);
+  s.used += 2;
+}
+
+int need(pmf_ctx* c, bool v, bool w, bool h) {
+  if (!c) return PMF_EINVAL;
+  c->hd_synced = false;        // (a new API call: whoever wrote the float32 H since the last one is noticed by k_hd_sync)
+  c->psd_fresh = false;
+  if (v && !c->have_v) return fail(c, PMF_EINVAL, "V has not been set (pmf_set_v_*)");
+  if (w && !c->have_w) return fail(c, PMF_EINVAL, "W has not been set (pmf_set_w_f32)");
+  if (h && !c->have_h) return fail(c, PMF_EINVAL, "H has not been set (pmf_set_h_f32)");
+  HIPCHK(c, hipSetDevice(c->device));
+  return PMF_OK;
+}
+
+// ---- an operand came from outside: the "<-" table at the flags' declarations (pmf_ctx) written as code.  Every entry point that
+// replaces V, W, H or CNMF's G calls one of these instead of writing flags; the transitions inside the algorithms stay where they happen.
+void v_replaced(pmf_ctx* c) { c->vnorm_valid = c->vnorm_local_valid = c->ps_valid = c->num_valid = c->trace_ready = c->c_valid = false; }
+void w_replaced(pmf_ctx* c, bool by_caller) {   // by_caller: uploaded or filled through the ABI (not the NNDSVD init, not a restored snapshot)
+  c->have_w = true; c->ps_valid = c->num_valid = c->trace_ready = c->w_implicit = false;
+  if (by_caller) c->cn_user_w = c->algo == PMF_ALGO_CNMF;   // (CNMF: the error is taken against this W until a G step rebinds it)
+}
+// hd_synced, hd_force: what the float64 H (SNMF, CNMF) is to the new float32 H -- written with it (true, false), the caller's float64
+// values beside their rounding (false, false), or not written at all (false, true: all of it is widened at its next use)
+void h_replaced(pmf_ctx* c, bool hd_synced, bool hd_force) {
+  c->have_h = true; c->g_valid = c->num_valid = c->trace_ready = false; c->g_parts = 0; c->hd_synced = hd_synced; c->hd_force = hd_force;
+}
+void g_replaced(pmf_ctx* c) {        // CNMF
+  c->have_g = true; c->cn_ab_valid = c->cn_l_valid = false;
+  if (!c->cn_user_w) { c->have_w = true; c->w_implicit = true; }   // cnmf.py:102-103,175: W = data G unless the caller set one
+}
+// the factors stay, sums over the data are formed anew: RNMF's D replaced, or (transport) the cross-rank sums take another way
+void sums_dropped(pmf_ctx* c, bool transport) {
+  c->ps_valid = c->trace_ready = false;
+  if (transport) c->vnorm_valid = c->c_valid = false;
+}
+
+}  // namespace

@@ -1,0 +1,71 @@
+// pmf_host_profile.h -- which launch site pmf_profile_enable times: choose_stat_site (KernelStat and the event brackets: pmf_host_ctx.h)
+// Host code of libpymf_hip.so: included by pmf_api.hip (the translation unit) in this order, nothing else includes it.
+#pragma once
+
+namespace {
+
+// Which launch site pmf_profile_enable times, with the ALGORITHMIC flops / bytes of ONE launch on THIS
+// rank's rows and the flops the kernel really executes (symmetry of W^T W,
+// reassociations) next to them.
+void choose_stat_site(pmf_ctx* c, bool gram) {
+  const double m = (double)c->m, n = (double)c->n, k = (double)c->k, nnz = (double)c->nnz;
+  KernelStat& st = c->stat;
+  const int old_site = st.site;
+  st.site = SITE_NONE; st.name = "none"; st.flops = st.bytes = st.exec_flops = 0.0;
+  char buf[96];
+  if (c->algo == PMF_ALGO_SNMF && gram) {
+    st.site = SITE_MATERIALIZE;                   // the only m-sized kernel of a Gram-space loop: W = V M, once
+    if (use_csr(c)) {
+      st.name = "k_csr_w_blocks(W = V M)";
+      st.flops = st.exec_flops = 2.0 * nnz * k;
+      st.bytes = 4.0 * m * k + 8.0 * nnz + 8.0 * (m + 1.0);      // W written once; CSR arrays read once
+    } else {
+      snprintf(buf, sizeof(buf), "k_rowgemm<%d,store>(W = V M^T)", c->NT);
+      st.name = buf;
+      st.flops = st.exec_flops = 2.0 * m * n * k;
+      st.bytes = 4.0 * (m * n + m * k);
+    }
+  } else if (c->algo == PMF_ALGO_SNMF && use_csr(c)) {
+    st.site = SITE_CSR_PASS;
+    st.name = "k_snmf_csr_mfma (one pass per iteration)";
+    st.flops = 4.0 * nnz * k + 4.0 * m * k * k;                  // SURVEY: SpMM, (.) inv, W^T V, W^T W
+    st.exec_flops = 4.0 * nnz * k + m * k * (k + 16.0);          // V M, W^T V, upper triangle of W^T W
+    st.bytes = 4.0 * m * k + 8.0 * nnz + 8.0 * (m + 1.0);
+  } else if (c->fused_wgs > 0 && c->algo != PMF_ALGO_NMFALS) {
+    st.site = SITE_FUSED;
+    st.name = c->fused8 ? c->path.c_str()
+                        : pmf_fused_kernel_name(c->NT, c->np, c->algo == PMF_ALGO_SNMF   ? FUSED_SNMF
+                                                          : c->algo == PMF_ALGO_BNMF ? FUSED_BNMF
+                                                          : c->algo == PMF_ALGO_RNMF ? FUSED_RNMF
+                                                                                     : FUSED_NMF);
+    // one pass over V does the four m-sized contractions of an iteration: F = 4 m n k + 4 m k^2
+    st.flops = 4.0 * m * n * k + 4.0 * m * k * k;
+    if (c->algo == PMF_ALGO_SNMF) {               // executes V M^T, W^T V and the upper triangle of W^T W
+      st.exec_flops = 4.0 * m * n * k + m * k * (k + 16.0);
+      st.bytes = 4.0 * (m * n + m * k);           // V read once, W written once
+    } else if (c->fused8) {                       // V H^T, W G, W^T V and ALL of W^T W (base split: no symmetry to use)
+      st.exec_flops = 4.0 * m * n * k + 4.0 * m * k * k;
+      st.bytes = 4.0 * (m * n + 2.0 * m * k);
+    } else {                                      // V H^T, W G, W^T V and the upper triangle of W^T W
+      st.exec_flops = 4.0 * m * n * k + 2.0 * m * k * k + m * k * (k + 16.0);
+      st.bytes = 4.0 * (m * n + 2.0 * m * k);     // V read once, W read and written once
+    }
+  } else if (c->algo == PMF_ALGO_NMFALS) {
+    st.site = SITE_NNQP_W;
+    if (c->opt_nnqp_quad && c->k <= 64 && (c->m >= 16384 || c->opt_nnqp_quad == 2)) snprintf(buf, sizeof(buf), "k_nnqp_quad(update_w)");
+    else if (c->k <= 64) snprintf(buf, sizeof(buf), "k_nnqp<%d>(update_w)", c->k <= 16 ? 16 : c->k <= 32 ? 32 : 64);
+    else if (nnqp_use_wave(c)) snprintf(buf, sizeof(buf), "k_nnqp_wave(update_w)");
+    else snprintf(buf, sizeof(buf), "k_nnqp_big<%d>(update_w)", pmf_nnqp_big_vpl(c->k));
+    st.name = buf;
+    st.bytes = 4.0 * (3.0 * m * k);               // right-hand sides read, warm start read, solution written
+  } else if ((c->algo == PMF_ALGO_NMF) && c->nb == 1) {
+    st.site = SITE_ROWGEMM_W;
+    snprintf(buf, sizeof(buf), "k_rowgemm<%d,nmf_w>", c->NT);
+    st.name = buf;
+    st.flops = st.exec_flops = 2.0 * m * n * k + 2.0 * m * k * k;
+    st.bytes = 4.0 * (m * n + 2.0 * m * k);
+  }
+  if (st.site != old_site) st.used = 0;
+}
+
+}  // namespace

@@ -402,7 +402,7 @@ __global__ __launch_bounds__(256) void k_add_f32(const float* __restrict__ a, co
     reinterpret_cast<f32x4*>(out)[q] = reinterpret_cast<const f32x4*>(a)[q] + reinterpret_cast<const f32x4*>(b)[q];
 }
 
-// dst += src (count a multiple of 4): the chunk sums of a product over very many columns (pmf_api.hip: PMF_WIDE_K).
+// dst += src (count a multiple of 4): the chunk sums of a product over very many columns (pmf_host_products.h: PMF_WIDE_K).
 __global__ __launch_bounds__(256) void k_acc_f32(float* __restrict__ dst, const float* __restrict__ src, int64_t count) {
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; 4 * q < count; q += (int64_t)gridDim.x * 256) {
     f32x4 d = reinterpret_cast<f32x4*>(dst)[q];

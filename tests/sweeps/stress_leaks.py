@@ -6,6 +6,7 @@ import numpy as np
 import ctypes
 import pymf_amd
 from pymf_amd import _lib
+from pymf_amd.rnmf import RNMF
 
 hip = ctypes.CDLL("libamdhip64.so")
 
@@ -23,19 +24,66 @@ def rss_mib():
 rs = np.random.RandomState(0)
 V = rs.random_sample((4096, 256)).astype(np.float32)
 bad = 0
-# 1. contexts created and closed over and over, every class
+# The added cases are sized so that the buffers only THEY own, leaked once per context, pass the 64 MiB threshold within the 55
+# counted repetitions (> 1.2 MiB per context; the large ones named here are >= 2 MiB each):
+#   BNMF 4096 x 256, 128 bases: dW1 2 MiB                      RNMF 4096 x 256: dD 4 MiB
+#   NMFNNLS 65536 x 256: dW1 4 MiB                             streamed NMF 8192 x 256, tiles of 2048 rows: dTile[2] 2 MiB each
+#   CNMF 256 x 2048, 128 bases: dGT dCnA dCnB dCnHn dCnHp 2 MiB each, dC 32 MiB
+#   SNMF 4096 x 2048, 128 bases, snapshots: dWsnap 2 MiB, dHsnap 5 MiB, dHdSnap 2 MiB
+#   SNMF on CSR 262144 x 256, 2 % non-zeros: dIndptr 2 MiB, dIndices and dVals 5 MiB each
+Vtall = rs.random_sample((65536, 256)).astype(np.float32)
+Vwide = rs.random_sample((256, 2048)).astype(np.float32)
+Vsnap = rs.random_sample((4096, 2048)).astype(np.float32) - 0.5
+try:
+    import scipy.sparse as sp
+    Vcsr = sp.random(262144, 256, density=0.02, format="csr", dtype=np.float32, random_state=rs)
+    Vcsr.data -= 0.5
+except ImportError:
+    Vcsr = None
+    print("scipy is not importable: the SNMF-on-CSR case is skipped")
+
+
+def plain(cls, data, k=16, **kw):
+    def run():
+        mdl = cls(data, num_bases=k)
+        mdl.factorize(niter=3, **kw)
+        return mdl
+    return run
+
+
+def streamed():                 # V never resident: row tiles through the two tile buffers
+    mdl = pymf_amd.NMF(Vtall[:8192], num_bases=16)
+    mdl.stream_rows = 2048
+    mdl.factorize(niter=3)
+    return mdl
+
+
+def snmf_snapshots():           # a second call on device-only factors: W is copied device to device first; then both snapshot buffers by name
+    mdl = pymf_amd.SNMF(Vsnap, num_bases=128)
+    mdl.factorize(niter=2)
+    mdl.factorize(niter=2)
+    mdl._ctx.snapshot_w(); mdl._ctx.snapshot_h()
+    return mdl
+
+
+cases = [plain(pymf_amd.NMF, V), plain(pymf_amd.SNMF, V - 0.5), plain(pymf_amd.NMFALS, V), plain(pymf_amd.BNMF, V, k=128),
+         plain(RNMF, V), plain(pymf_amd.CNMF, Vwide, k=128), plain(pymf_amd.NMFNNLS, Vtall), streamed, snmf_snapshots]
+if Vcsr is not None:
+    cases.append(plain(pymf_amd.SNMF, Vcsr, compute_err=False))   # (no error on scipy.sparse data, as in the reference)
+# 1. contexts created and closed over and over, every class, every kind of buffer (dense, CSR, streamed, snapshots)
 _lib.load()
 m0 = None
+t_start = time.time()
 for rep in range(60):
-    for cls, kw in ((pymf_amd.NMF, {}), (pymf_amd.SNMF, {}), (pymf_amd.NMFALS, {})):
-        mdl = cls(V if cls is not pymf_amd.SNMF else V - 0.5, num_bases=16)
-        mdl.factorize(niter=3)
+    for run in cases:
+        mdl = run()
         if not np.all(np.isfinite(mdl.W)) or not np.all(np.isfinite(mdl.H)):
             bad += 1
         mdl._ctx.close(); mdl._ctx = None
     if rep == 4:
         m0, r0 = free_mib(), rss_mib()
 m1, r1 = free_mib(), rss_mib()
+print("contexts: %d in %.0f s" % (60 * len(cases), time.time() - t_start))
 print("contexts: free device memory %.0f -> %.0f MiB, max RSS %.0f -> %.0f MiB" % (m0, m1, r0, r1))
 if m0 - m1 > 64 or r1 - r0 > 256:
     bad += 1

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """update_w against the float64 oracle as the number of columns grows (one accumulation chain of V H^T spans n / 4 fp32 MFMA
-steps up to 65 536 columns, chunks of 65 536 beyond: PMF_WIDE_K in pmf_api.hip): mean / std / max relative error of W."""
+steps up to 65 536 columns, chunks of 65 536 beyond: PMF_WIDE_K in pmf_host_products.h): mean / std / max relative error of W."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

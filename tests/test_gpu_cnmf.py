@@ -108,6 +108,24 @@ def test_float64_h_and_g_round_trip_exactly(pm):
     ctx.close()
 
 
+def test_a_filled_w_is_the_w_that_is_read_back(pm):
+    """pmf_set_g_f64 binds W = V G (materialised when it is read); pmf_fill_w_uniform behind it replaces W like
+    pmf_set_w_* does: the W read back is the fill, bit for bit, not V G written over it."""
+    from pymf_amd import _lib
+    m, n, k = 96, 200, 12
+    rs = np.random.RandomState(4)
+    ctx = _lib.Context(_lib.ALGO_CNMF, m, n, k)
+    ctx.set_v_dense(rs.random_sample((m, n)).astype(np.float32))
+    ctx.set_g(rs.random_sample((n, k)) / 3.0)
+    ctx.fill_w_uniform(7)
+    W = ctx.get_w()
+    ctx.close()
+    ref = _lib.Context(_lib.ALGO_NMF, m, n, k)
+    ref.fill_w_uniform(7)
+    assert np.array_equal(W, ref.get_w())
+    ref.close()
+
+
 def _golden_state(name="cnmf_300x64_k6"):
     d = load_golden(name)
     V = d["V"].astype(np.float64)

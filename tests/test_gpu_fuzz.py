@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
                                        ("fuzz_sequences.py", ["2031", "30"]),
                                        ("fuzz_abi_sequences.py", ["2040", "50"]),  # ... of C-ABI calls on one context, resident and streamed passes mixed
                                        ("threads_probe.py", []),                 # 24 host threads, one object each: bit-identical to sequential
-                                       ("stress_leaks.py", []),                  # 180 contexts, 20 000-iteration loops: memory comes back
+                                       ("stress_leaks.py", []),                  # contexts of every class 60 times over, 20 000-iteration loops: memory comes back
                                        ("huge_probe.py", ["20971520"]),          # V of 5.4e9 elements (> 2^32): W rows vs the oracle, one-pass vs two-pass
                                        ("huge_probe2.py", ["20971520"]),         # ... NMFALS (KKT), SNMF on it; NMF 1 024 x 1 000 000
                                        ("huge_probe3.py", ["20971520", "256"]),  # ... 256 bases: W of 5.4e9 elements on the wide-base path

@@ -1469,3 +1469,24 @@ def test_long_run_on_a_storage_sensitive_problem(pm):
     # ... and the library is where the float64 oracle is
     assert rel_fro(a.W, exact.W, what="W vs the float64 oracle, 130 iterations") < 2e-5
     assert rel_fro(a.H, exact.H, what="H vs the float64 oracle, 130 iterations") < 2e-5
+
+
+def test_a_filled_w_behind_a_gram_space_snmf_loop_is_read_back(pm):
+    """pmf_factorize in Gram space (SNMF, snmf_gram = 1) never writes W inside the loop and materialises W = V M before it
+    returns; pmf_fill_w_uniform behind it replaces W: the W read back is the fill, bit for bit."""
+    from pymf_amd import _lib
+    m, n, k = 2100, 256, 16
+    rs = np.random.RandomState(5)
+    c = _lib.Context(_lib.ALGO_SNMF, m, n, k)
+    c.set_v_dense(rs.random_sample((m, n)).astype(np.float32) - 0.4)
+    c.fill_w_uniform(42); c.fill_h_uniform(43)
+    c.set_option("snmf_gram", 1)
+    _, done, _ = c.factorize(3, compute_err=False)
+    assert done == 3
+    c.fill_w_uniform(7)
+    W = c.get_w()
+    c.close()
+    ref = _lib.Context(_lib.ALGO_SNMF, m, n, k)
+    ref.fill_w_uniform(7)
+    assert np.array_equal(W, ref.get_w())
+    ref.close()
