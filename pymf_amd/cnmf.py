@@ -22,7 +22,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .nmf import NMF, _fingerprint, _is_sparse
+from .nmf import NMF, _is_sparse
 
 __all__ = ["CNMF"]
 
@@ -30,7 +30,8 @@ __all__ = ["CNMF"]
 class CNMF(NMF):
     _SHIPPED = True
     _ALGO = _lib.ALGO_CNMF
-    _REBIND_W = True                 # cnmf.py:175 rebinds self.W
+    _FACTORS = ("G", "H", "W")       # upload order
+    _SKIP_MISSING_FACTORS = True     # init_h synchronises before H (and, unless the caller set them, G and W) exists
     _HOOKS = ("frobenius_norm", "converged")   # the reference's own loop calls no other hook (cnmf.py:156-187)
     _KMEANS_NITER = 10               # cnmf.py:86
 
@@ -45,9 +46,6 @@ class CNMF(NMF):
             raise ValueError("CNMF: streamed data (stream_rows) is not supported: C = data^T data needs the data resident")
         if self._world().size > 1:
             raise NotImplementedError("CNMF: one rank only (a multi-rank world is not supported)")
-
-    def _upload_sparse(self, ctx):
-        raise TypeError("CNMF: scipy.sparse data is not supported (dense data only)")
 
     # ---- the reference's hooks -----------------------------------------------------------------------
     def update_w(self):                                        # cnmf.py:72-73
@@ -71,57 +69,24 @@ class CNMF(NMF):
         ctx.cnmf_init(sel, self._KMEANS_NITER)
         for name, shape in (("H", (k, n)), ("G", (n, k)), ("W", (self._data_dimension, k))):
             if name == "H" or not self._has(name):
-                self.__dict__["_" + name] = np.zeros(shape)   # filled from the device when read
-                self.__dict__["_%s_fp" % name.lower()] = None
-                self._host_stale.add(name)
+                self._on_device_only(name, shape)
+
+    def _on_device_only(self, name, shape):
+        """A factor that exists on the device alone so far: its host array is filled when it is read."""
+        self._factor_set(name, np.zeros(shape))
+        self._host_stale.add(name)
 
     # ---- host <-> device ---------------------------------------------------------------------------------
-    def _sync_to_device_timed(self, ctx, with_data):
-        if with_data and (not self._in_loop or not self._loop_data_checked):
-            self._loop_data_checked = True
-            self._upload_data(ctx)
-        for name, setter in (("G", ctx.set_g), ("H", ctx.set_h), ("W", ctx.set_w)):
-            if name in self._host_stale or not self._has(name):
-                continue                                       # the device copy is the newer one / not there yet
-            fp_attr = "_%s_fp" % name.lower()
-            if (self.__dict__.get(fp_attr) is not None and name not in self._handed
-                    and not self._held_elsewhere(name)):
-                continue
-            arr = self.__dict__["_" + name]
-            if not np.issubdtype(np.asarray(arr).dtype, np.floating):
-                raise TypeError("%s must be a floating-point array" % name)
-            fp = _fingerprint(arr)
-            if self.__dict__.get(fp_attr) != fp:
-                self._uploaded = True
-                setter(np.asarray(arr))
-                self.__dict__[fp_attr] = fp
-            del arr
-            self._handed.discard(name)
-        return ctx
-
-    def _refresh_host(self, name):
-        ctx = self._context()
-        self._host_stale.discard(name)
+    def _download(self, ctx, name, cur):
         if name == "H":                                        # cnmf.py:167 rebinds H (float64, exact)
-            self.__dict__["_H"] = ctx.get_h64()
-        elif name == "W":                                      # cnmf.py:175 rebinds W = data G
-            self.__dict__["_W"] = ctx.get_w().astype(np.float64)
-        else:                                                  # cnmf.py:174 updates G in place
-            cur = self.__dict__["_G"]
-            np.copyto(cur, ctx.get_g(), casting="unsafe")
-        self.__dict__["_%s_fp" % name.lower()] = _fingerprint(self.__dict__["_" + name])
+            return ctx.get_h64()
+        if name == "W":                                        # cnmf.py:175 rebinds W = data G
+            return ctx.get_w().astype(np.float64)
+        np.copyto(cur, ctx.get_g(), casting="unsafe")          # cnmf.py:174 updates G in place
+        return cur
 
-    def _pull(self, ctx, want_w, want_h):
-        NMF._pull(self, ctx, want_w, want_h)
-        if want_w:
-            self._host_stale.add("G")
-            if not self._defer_pull and self._held_elsewhere("G"):
-                self._refresh_host("G")
-
-    def __getstate__(self):
-        st = NMF.__getstate__(self)
-        st["_g_fp"] = None
-        return st
+    def _moved(self, w_ran, h_ran):
+        return NMF._moved(self, w_ran, h_ran) + (("G",) if w_ran else ())     # a W step is a G step: W = data G
 
     def frobenius_norm(self):
         """||data - W H|| (nmf.py:100-114): W = data G on the device, or the W the caller set."""
@@ -142,51 +107,17 @@ class CNMF(NMF):
         if not self._has("G"):
             self.G                                             # AttributeError, as the reference's self.G (cnmf.py:159)
         if not self._has("W"):                                 # H and G given, no W: W = data G on the device
-            self.__dict__["_W"] = np.zeros((self._data_dimension, self._num_bases))
-            self.__dict__["_w_fp"] = None
-            self._host_stale.add("W")
+            self._on_device_only("W", (self._data_dimension, self._num_bases))
         self._tick("init", t_call)
         self.ferr = np.zeros(niter)                            # cnmf.py:154
         if self._hooks_overridden() or show_progress:
             return self._factorize_by_hooks(niter, compute_w, compute_h, compute_err)
         ctx = self._sync_to_device()
-        ferr, done, conv_at = ctx.factorize(niter, compute_w, compute_h, compute_err, conv_eps=self._EPS)
-        self._last_iters = done
-        self._pull(ctx, compute_w and done > 0, compute_h and done > 0)
-        self.last_call_ms["loop"] = ctx.last_loop_ms()
-        self._tick("total", t_call)
-        for i in range(done):
-            if compute_err:
-                self.ferr[i] = ferr[i]
-                self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter) + ' FN:' + str(self.ferr[i]))
-            else:
-                self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter))
-        if compute_err and conv_at >= 0:                       # cnmf.py:184-187
-            self.ferr = self.ferr[:conv_at]
+        result = ctx.factorize(niter, compute_w, compute_h, compute_err, conv_eps=self._EPS)
+        self._after_device_loop(ctx, niter, result, compute_w, compute_h, compute_err, t_call)
 
-    def _factorize_by_hooks(self, niter, compute_w, compute_h, compute_err):
-        """cnmf.py:156-187 one iteration per device call, with the (overridden) frobenius_norm / converged in between."""
-        self._defer_pull = True
-        self._in_loop = True
-        self._loop_data_checked = False
-        done = 0
-        try:
-            for i in range(niter):
-                ctx = self._sync_to_device()
-                ctx.factorize(1, compute_w, compute_h, False)
-                self._pull(ctx, compute_w, compute_h)
-                done = i + 1
-                if compute_err:
-                    self.ferr[i] = self.frobenius_norm()
-                    self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter) + ' FN:' + str(self.ferr[i]))
-                else:
-                    self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter))
-                if i > 1 and compute_err:
-                    if self.converged(i):
-                        self.ferr = self.ferr[:i]
-                        break
-        finally:
-            self._defer_pull = False
-            self._in_loop = False
-            self._last_iters = done
-            self._flush_host()
+    def _hook_iteration(self, compute_w, compute_h):
+        """cnmf.py:156-175: one iteration per device call, the (overridden) frobenius_norm / converged run in between."""
+        ctx = self._sync_to_device()
+        ctx.factorize(1, compute_w, compute_h, False)
+        self._pull(ctx, self._moved(compute_w, compute_h))

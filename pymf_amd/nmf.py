@@ -13,6 +13,9 @@ ONE C call (`pmf_factorize`).  When a subclass (or the instance) overrides any o
 for live log lines, `factorize()` runs the reference's loop hook by hook -- every
 shipped hook is itself one C call -- so user plug-ins behave as in the reference.
 
+The factors live on the device between calls.  Each class lists its own (`_FACTORS`: W and H, CNMF also G); the upload
+loop (`_sync_to_device_timed`), `_refresh_host`, `_pull` and the loops of `factorize()` are NMF's, for every class.
+
 Host-visible state follows the reference: W/H are created lazily, W first
 (nmf.py:173-177), default float64 (nmf.py:117,120); NMF writes results back IN
 PLACE into the existing arrays (nmf.py:125-126,131-132) keeping their dtype;
@@ -47,6 +50,10 @@ def _fingerprint(a):
     its bytes (one multi-threaded pass at memory speed).  Any in-place edit -- a poke, a swap of two
     rows, a permutation of the bases -- changes it, so the device copy is refreshed."""
     return _lib.host_checksum(a)
+
+
+def _fp_attr(name):
+    return "_%s_fp" % name.lower()       # `_w_fp`, `_h_fp`: the digest of the host array that the device copy equals
 
 
 def _draw_rows(m_total, ncols, lo, hi, chunk=65536):
@@ -131,6 +138,10 @@ class NMF(object):
 
     _EPS = 10 ** -8          # nmf.py:69
     _ALGO = _lib.ALGO_NMF
+    #: The factors that live on the device between calls, in upload order (the library sees the setters in this order):
+    #: the digests (`_w_fp`, ...), the upload loop, _refresh_host, _pull and __getstate__ work from this table.
+    _FACTORS = ("W", "H")
+    _SKIP_MISSING_FACTORS = False    # a missing W / H raises AttributeError, as the reference's self.W would (CNMF: skipped)
     _REBIND_W = False        # SNMF rebinds self.W (snmf.py:70); NMF mutates in place
     _SHIPPED = True          # marks the classes whose hooks are the built-in C calls
     _HOOKS = ("update_w", "update_h", "frobenius_norm", "converged")
@@ -153,27 +164,22 @@ class NMF(object):
     eager_factors = False
 
     def __init__(self, data, num_bases=4):
-        def setup_logging():                                   # nmf.py:73-90
-            self._logger = logging.getLogger("pymf")
-            if len(self._logger.handlers) < 1:
-                ch = logging.StreamHandler()
-                ch.setLevel(logging.DEBUG)
-                ch.setFormatter(logging.Formatter("%(asctime)s [%(levelname)s] %(message)s"))
-                self._logger.addHandler(ch)
-
-        setup_logging()
+        self._logger = logging.getLogger("pymf")               # nmf.py:73-90
+        if len(self._logger.handlers) < 1:
+            ch = logging.StreamHandler()
+            ch.setLevel(logging.DEBUG)
+            ch.setFormatter(logging.Formatter("%(asctime)s [%(levelname)s] %(message)s"))
+            self._logger.addHandler(ch)
         self.data = data                                       # nmf.py:93 (by reference)
         self._num_bases = num_bases                            # nmf.py:94
         (self._data_dimension, self._num_samples) = self.data.shape   # nmf.py:97
         self._ctx = None
         self._v_src = None       # the `data` object currently resident on the device
         self._v_fp = None        # ... and the digest of its bytes at upload time
-        self._w_fp = None        # digest of the host W/H the device copies equal
-        self._h_fp = None
+        self.__dict__.update((_fp_attr(name), None) for name in self._FACTORS)   # digest of the host W/H the device copies equal
         self._host_stale = set() # factors whose DEVICE copy is newer than the host array
         self._handed = set()     # factors whose host array was read through .W / .H since it was last synchronised
-        self._defer_pull = False
-        self._in_loop = False
+        self._in_loop = False    # inside factorize()'s hook loop: `data` is checked once, the factors stay on the device
         self._loop_data_checked = False
         #: wall-clock ms of the last factorize() call's parts: ctx (context creation), init (lazy init_w / init_h),
         #: upload (digests + host -> device copies of data, W, H), loop (device loop), total
@@ -198,7 +204,7 @@ class NMF(object):
     def _factor_set(self, name, value):
         self.__dict__["_" + name] = value
         self.__dict__.setdefault("_host_stale", set()).discard(name)
-        self.__dict__["_%s_fp" % name.lower()] = None          # host is newer: upload at the next call
+        self.__dict__[_fp_attr(name)] = None                   # host is newer: upload at the next call
 
     def _has(self, name):
         """hasattr(self, 'W') without reading the property (a read refreshes the host array)."""
@@ -359,12 +365,15 @@ class NMF(object):
                     self._v_src = self.data
             else:
                 self._upload_data(ctx)
-        for name, fp_attr, setter in (("W", "_w_fp", ctx.set_w), ("H", "_h_fp", ctx.set_h)):
+        for name in self._FACTORS:
             if name in self._host_stale:          # the device copy is the newer one
                 continue
             if not self._has(name):
+                if self._SKIP_MISSING_FACTORS:
+                    continue
                 getattr(self, name)               # AttributeError, as the reference's self.W would raise
-            if (getattr(self, fp_attr) is not None and name not in self._handed
+            fp_attr = _fp_attr(name)
+            if (self.__dict__.get(fp_attr) is not None and name not in self._handed
                     and not self._held_elsewhere(name)):
                 continue                          # equal to the device copy and out of everybody's reach since
             arr = self.__dict__["_" + name]
@@ -372,38 +381,40 @@ class NMF(object):
                 # reference: `W *= dot(...)` on an integer W raises UFuncTypeError
                 raise TypeError("%s must be a floating-point array" % name)
             fp = _fingerprint(arr)
-            if getattr(self, fp_attr) != fp:
+            if self.__dict__.get(fp_attr) != fp:
                 self._uploaded = True
-                setter(arr)
-                setattr(self, fp_attr, fp)
+                getattr(ctx, "set_" + name.lower())(arr)
+                self.__dict__[fp_attr] = fp
             del arr
             self._handed.discard(name)
         return ctx
 
     def _refresh_host(self, name):
-        """Bring the host array of W or H up to date with the device (the deferred half of _pull)."""
+        """Bring the host array of a factor up to date with the device (the deferred half of _pull)."""
         ctx = self._context()
         self._host_stale.discard(name)
-        if name == "W":
-            cur = self.__dict__["_W"]
-            if self._REBIND_W:
-                w = ctx.get_w()
-                self.__dict__["_W"] = w.astype(cur.dtype, copy=False) if cur.dtype != np.float32 else w
-            elif not (hasattr(ctx, "get_w_into") and ctx.get_w_into(cur)):   # in place, nmf.py:131-132 (float64: widened on the device)
-                np.copyto(cur, ctx.get_w(), casting="same_kind")
-            self._w_fp = _fingerprint(self.__dict__["_W"])
-        else:
-            cur = self.__dict__["_H"]
-            if not (hasattr(ctx, "get_h_into") and ctx.get_h_into(cur)):     # in place, nmf.py:125-126
-                np.copyto(cur, ctx.get_h(), casting="same_kind")
-            self._h_fp = _fingerprint(self.__dict__["_H"])
+        self._host_is_current(name, self._download(ctx, name, self.__dict__["_" + name]))
 
-    def _pull(self, ctx, want_w, want_h):
-        for name, want in (("W", want_w), ("H", want_h)):
-            if not want:
-                continue
+    def _download(self, ctx, name, cur):
+        """The device's values of factor `name`: written into `cur`, its host array, or a new array to bind in its place."""
+        if name == "W" and self._REBIND_W:
+            return ctx.get_w().astype(cur.dtype, copy=False)
+        into = "get_%s_into" % name.lower()
+        if not (hasattr(ctx, into) and getattr(ctx, into)(cur)):   # in place, nmf.py:125-126,131-132 (float64: widened on the device)
+            np.copyto(cur, getattr(ctx, "get_" + name.lower())(), casting="same_kind")
+        return cur
+
+    def _host_is_current(self, name, arr):            # `arr`, from now on the host array, holds what the device copy holds
+        self.__dict__["_" + name] = arr
+        self.__dict__[_fp_attr(name)] = _fingerprint(arr)
+
+    def _moved(self, w_ran, h_ran):                   # the factors that a W step and / or an H step changed on the device
+        return (("W",) if w_ran else ()) + (("H",) if h_ran else ())
+
+    def _pull(self, ctx, moved):
+        for name in moved:
             self._host_stale.add(name)
-            if not self._defer_pull and self._held_elsewhere(name):
+            if not self._in_loop and self._held_elsewhere(name):
                 self._refresh_host(name)          # somebody holds the array: the reference's in-place update
 
     def _flush_host(self, force=False):
@@ -414,10 +425,10 @@ class NMF(object):
     def __getstate__(self):                       # pickling / copying: host arrays up to date, no device handle
         self._flush_host(force=True)
         st = dict(self.__dict__)
-        st["_ctx"] = None
-        st["_v_src"] = st["_v_fp"] = st["_w_fp"] = st["_h_fp"] = None
+        st["_ctx"] = st["_v_src"] = st["_v_fp"] = None
+        st.update((_fp_attr(name), None) for name in self._FACTORS)
         st["_host_stale"], st["_handed"] = set(), set()       # the copy shares no bookkeeping with the original
-        st["_defer_pull"] = st["_in_loop"] = st["_loop_data_checked"] = False
+        st["_in_loop"] = st["_loop_data_checked"] = False
         st.pop("_span", None)
         return st
 
@@ -454,7 +465,7 @@ class NMF(object):
             self._stream_iteration(ctx, rows, False, True, False)
         else:
             ctx.update_h()
-        self._pull(ctx, False, True)
+        self._pull(ctx, ("H",))
 
     def update_w(self):                                        # nmf.py:128-132
         ctx = self._sync_to_device()
@@ -468,7 +479,7 @@ class NMF(object):
         except Exception:                                      # e.g. SNMF: LinAlgError behind a singular H H^T
             self._after_failed_w_step(ctx, snap)
             raise
-        self._pull(ctx, True, False)
+        self._pull(ctx, ("W",))
 
     #: True for classes whose W step can raise (SNMF: np.linalg.inv on a singular H H^T, snmf.py:69)
     _W_STEP_MAY_FAIL = False
@@ -525,11 +536,7 @@ class NMF(object):
     def factorize(self, niter=1, show_progress=False,
                   compute_w=True, compute_h=True, compute_err=True):
         """Factorize s.t. WH = data (nmf.py:141-202)."""
-        if show_progress:                                      # nmf.py:166-169
-            self._logger.setLevel(logging.INFO)
-        else:
-            self._logger.setLevel(logging.ERROR)
-
+        self._logger.setLevel(logging.INFO if show_progress else logging.ERROR)   # nmf.py:166-169
         t_call = time.perf_counter()
         self.last_call_ms = {}
         if not self._has('W'):                                 # nmf.py:173-174
@@ -555,19 +562,11 @@ class NMF(object):
                 late = None
                 self._upload_data(ctx)
         if rows:                                               # a Python loop already: logs as it runs
-            ferr, done, conv_at = self._factorize_streamed(ctx, rows, niter, compute_w, compute_h, compute_err)
-            self._last_iters = done
-            self._pull(ctx, compute_w and done > 0, compute_h and done > 0)
-            if compute_err:
-                self.ferr[:done] = ferr[:done]
-                if conv_at >= 0:                               # nmf.py:198-202
-                    self.ferr = self.ferr[:conv_at]
-            return
+            result = self._factorize_streamed(ctx, rows, niter, compute_w, compute_h, compute_err)
         else:
             try:
                 try:
-                    ferr, done, conv_at = ctx.factorize(niter, compute_w, compute_h, compute_err,
-                                                        conv_eps=self._EPS)
+                    result = ctx.factorize(niter, compute_w, compute_h, compute_err, conv_eps=self._EPS)
                 except Exception:
                     if late is None or not late.data_changed():
                         raise
@@ -576,8 +575,7 @@ class NMF(object):
                     # as soon as the digest knew).  W and H go back to what they were, the new bytes go up, and the call
                     # starts again -- what the reference computes, which reads self.data[:,:] afresh (nmf.py:123,129)
                     late.restart()
-                    ferr, done, conv_at = ctx.factorize(niter, compute_w, compute_h, compute_err,
-                                                        conv_eps=self._EPS)
+                    result = ctx.factorize(niter, compute_w, compute_h, compute_err, conv_eps=self._EPS)
             except Exception:
                 # the device factors are in an unknown state (e.g. behind a singular H H^T): W goes back to the
                 # snapshot (or to the host array where that is the current one), H to the host array (a class
@@ -590,21 +588,27 @@ class NMF(object):
                 # a flag left set would make the NEXT pmf_factorize return at once with iters_done = 0 and no error (round-5 advisor)
                 if late is not None:
                     late.finish()
-        self._last_iters = done
-        self._pull(ctx, compute_w and done > 0, compute_h and done > 0)
-        if hasattr(ctx, "last_loop_ms"):
-            self.last_call_ms["loop"] = ctx.last_loop_ms()
-        self._tick("total", t_call)
+        self._after_device_loop(ctx, niter, result, compute_w, compute_h, compute_err, None if rows else t_call)
 
-        for i in range(done):                                  # nmf.py:189-194
-            if compute_err:
-                self.ferr[i] = ferr[i]
-                self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter) +
-                                  ' FN:' + str(self.ferr[i]))
-            else:
-                self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter))
+    def _after_device_loop(self, ctx, niter, result, compute_w, compute_h, compute_err, t_call=None):
+        """What follows a loop that ran without the hooks, `result` being Context.factorize's triple.  Given t_call (the loop
+        was ONE device call), "loop" / "total" are recorded and the log lines written: the streamed loop logs as it runs."""
+        ferr, done, conv_at = result
+        self._last_iters = done
+        self._pull(ctx, self._moved(compute_w and done > 0, compute_h and done > 0))
+        if compute_err:
+            self.ferr[:done] = ferr[:done]
+        if t_call is not None:
+            if hasattr(ctx, "last_loop_ms"):
+                self.last_call_ms["loop"] = ctx.last_loop_ms()
+            self._tick("total", t_call)
+            for i in range(done):                              # nmf.py:189-194
+                self._log_iteration(i, niter, self.ferr[i] if compute_err else None)
         if compute_err and conv_at >= 0:                       # nmf.py:198-202
             self.ferr = self.ferr[:conv_at]
+
+    def _log_iteration(self, i, niter, err=None):              # nmf.py:191-194; err: None without compute_err
+        self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter) + ('' if err is None else ' FN:' + str(err)))
 
     #: The digest of a large `data` before every factorize() (check_data) runs BESIDE the device loop instead of in front of
     #: it: the loop starts on the resident copy at once; if the bytes turn out to have changed since the upload the loop is
@@ -630,32 +634,30 @@ class NMF(object):
         """The reference's loop (nmf.py:182-202), one hook call at a time, log lines as it runs.
         W and H stay on the device between the hooks; the host arrays are refreshed when a hook (or
         the user) reads `.W` / `.H`, and in any case before factorize() returns."""
-        self._defer_pull = True
         self._in_loop = True
         self._loop_data_checked = False
         done = 0
         try:
             for i in range(niter):
-                if compute_w:
-                    self.update_w()
-                if compute_h:
-                    self.update_h()
+                self._hook_iteration(compute_w, compute_h)
                 done = i + 1
                 if compute_err:
                     self.ferr[i] = self.frobenius_norm()
-                    self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter) +
-                                      ' FN:' + str(self.ferr[i]))
-                else:
-                    self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter))
+                self._log_iteration(i, niter, self.ferr[i] if compute_err else None)
                 if i > 1 and compute_err:
                     if self.converged(i):
                         self.ferr = self.ferr[:i]
                         break
         finally:
-            self._defer_pull = False
             self._in_loop = False
             self._last_iters = done
             self._flush_host()
+
+    def _hook_iteration(self, compute_w, compute_h):           # nmf.py:183-187
+        if compute_w:
+            self.update_w()
+        if compute_h:
+            self.update_h()
 
     def _factorize_streamed(self, ctx, rows, niter, compute_w, compute_h, compute_err):
         """The loop of nmf.py:182-202 with one streamed pass per iteration; same return triple as
@@ -667,10 +669,8 @@ class NMF(object):
             done = i + 1
             if compute_err:
                 ferr[i] = e
-                self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter) + ' FN:' + str(ferr[i]))
-                if i > 1 and abs(ferr[i] - ferr[i - 1]) / self._num_samples < self._EPS:   # nmf.py:134-139,198
-                    conv_at = i
-                    break
-            else:
-                self._logger.info('Iteration ' + str(i + 1) + '/' + str(niter))
+            self._log_iteration(i, niter, ferr[i] if compute_err else None)
+            if compute_err and i > 1 and abs(ferr[i] - ferr[i - 1]) / self._num_samples < self._EPS:   # nmf.py:134-139,198
+                conv_at = i
+                break
         return ferr, done, conv_at

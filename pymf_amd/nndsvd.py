@@ -17,7 +17,7 @@ import logging
 import numpy as np
 
 from . import _lib
-from .nmf import NMF, _fingerprint
+from .nmf import NMF
 
 __all__ = ["NNDSVD"]
 
@@ -42,8 +42,8 @@ class NNDSVD(NMF):
             ctx.nndsvd_init()
             np.copyto(self.W, ctx.get_w(), casting="same_kind")
             np.copyto(self.H, ctx.get_h(), casting="same_kind")
-            self._w_fp = _fingerprint(self.W)
-            self._h_fp = _fingerprint(self.H)
+            self._host_is_current("W", self.W)                  # (this object's context holds exactly these)
+            self._host_is_current("H", self.H)
         else:
             ctx = _lib.Context(_lib.ALGO_NMF, self._num_samples, self._data_dimension,
                                self._num_bases, device=w.local_rank)
@@ -58,10 +58,7 @@ class NNDSVD(NMF):
     def factorize(self, niter=1, show_progress=False,
                   compute_w=True, compute_h=True, compute_err=True):
         """One pass, whatever niter / compute_w / compute_h say (nndsvd.py:108-114)."""
-        if show_progress:                                       # nmf.py:166-169
-            self._logger.setLevel(logging.INFO)
-        else:
-            self._logger.setLevel(logging.ERROR)
+        self._logger.setLevel(logging.INFO if show_progress else logging.ERROR)   # nmf.py:166-169
         if not self._has('W'):
             self.init_w()
         if not self._has('H'):
@@ -72,6 +69,4 @@ class NNDSVD(NMF):
         self.update_h()
         if compute_err:
             self.ferr[0] = self.frobenius_norm()
-            self._logger.info('Iteration 1/1 FN:' + str(self.ferr[0]))
-        else:
-            self._logger.info('Iteration 1/1')
+        self._log_iteration(0, 1, self.ferr[0] if compute_err else None)

@@ -416,3 +416,209 @@ def test_an_interrupted_call_does_not_leave_the_abort_request_behind():
         mdl.factorize(niter=3, compute_err=False)
     assert "abort(1)" in mdl._ctx.log and mdl._ctx.log[-1] == "abort(0)", mdl._ctx.log
     assert mdl._ctx.aborted is False
+
+
+class _CnmfCtx(_CountingCtx):
+    """The counting double with the calls pymf_amd.CNMF makes (set_g / get_g / get_h64 / cnmf_init / last_loop_ms), a log of
+    the boundary traffic in order, and arithmetic that is only recognisable: an iteration adds 1 to G (W = V G) and to H."""
+
+    def __init__(self, m, n, k):
+        _CountingCtx.__init__(self, m, n, k)
+        self.up["G"] = self.down["G"] = 0
+        self.log = []
+        self.W = self.H = self.G = None
+
+    def set_v_dense(self, V):
+        self.log.append("set_v"); _CountingCtx.set_v_dense(self, V)
+
+    def set_w(self, W):
+        self.log.append("set_w"); _CountingCtx.set_w(self, W)
+
+    def set_h(self, H):
+        self.log.append("set_h"); _CountingCtx.set_h(self, H)
+
+    def set_g(self, G):
+        self.log.append("set_g"); self.G = np.array(G, dtype=np.float64); self.up["G"] += 1
+
+    def get_g(self):
+        self.down["G"] += 1
+        return self.G.copy()
+
+    def get_h64(self):
+        self.down["H"] += 1
+        return self.H.copy()
+
+    def cnmf_init(self, sel, km_niter=10):
+        self.log.append("cnmf_init")
+        self.H = np.full((self.k, self.n), 0.2)
+        if self.G is None:
+            self.G = np.full((self.n, self.k), 0.01)
+        if self.W is None:
+            self.W = self.V @ self.G
+
+    def factorize(self, niter, compute_w=True, compute_h=True, compute_err=True, conv_eps=1e-8):
+        self.log.append("factorize(%d)" % niter)
+        for _ in range(niter):
+            if compute_w:
+                self.G = self.G + 1.0
+                self.W = self.V @ self.G
+            if compute_h:
+                self.H = self.H + 1.0
+        return np.arange(max(niter, 1), 0, -1.0), niter, -1
+
+    def last_loop_ms(self):
+        return 0.25
+
+
+def _cnmf_with_double(m=20, n=10, k=3, seed=0, cls=None):
+    rs = np.random.RandomState(seed)
+    mdl = (cls or pymf_amd.CNMF)(rs.randn(m, n).astype(np.float32), num_bases=k)
+    mdl._ctx = _CnmfCtx(m, n, k)
+    return mdl
+
+
+def test_cnmf_factors_stay_on_the_device_until_they_are_read():
+    """init through factorize(), a second factorize(), reads of .G / .H / .W: nothing goes up but `data`, every factor comes
+    down once, when it is read; G comes back in place (cnmf.py:174), H and W as new float64 arrays (cnmf.py:167,175)."""
+    mdl = _cnmf_with_double()
+    ctx = mdl._ctx
+    mdl.factorize(niter=2)
+    assert ctx.log == ["set_v", "cnmf_init", "factorize(2)"], ctx.log
+    assert mdl._host_stale == {"G", "H", "W"} and mdl._handed == set()
+    assert mdl._g_fp is None and mdl._h_fp is None and mdl._w_fp is None
+    assert ctx.up == {"W": 0, "H": 0, "G": 0, "V": 1} and ctx.down == {"W": 0, "H": 0, "G": 0}
+    assert mdl.last_call_ms["loop"] == 0.25 and set(mdl.last_call_ms) >= {"init", "upload", "loop", "total"}
+    np.testing.assert_array_equal(mdl.ferr, [2.0, 1.0])
+    mdl.factorize(niter=3)
+    assert ctx.log[3:] == ["factorize(3)"] and mdl._host_stale == {"G", "H", "W"}
+    assert ctx.up == {"W": 0, "H": 0, "G": 0, "V": 1} and ctx.down == {"W": 0, "H": 0, "G": 0}
+    g_host = mdl.__dict__["_G"]
+    np.testing.assert_array_equal(mdl.G, np.full((10, 3), 5.01))
+    assert mdl.__dict__["_G"] is g_host                               # in place
+    del g_host
+    assert ctx.down == {"W": 0, "H": 0, "G": 1} and mdl._host_stale == {"H", "W"} and mdl._handed == {"G"}
+    assert mdl._g_fp is not None
+    h_host = mdl.__dict__["_H"]
+    np.testing.assert_array_equal(mdl.H, np.full((3, 10), 5.2))
+    assert mdl.__dict__["_H"] is not h_host and mdl.H.dtype == np.float64     # rebound
+    assert ctx.down == {"W": 0, "H": 1, "G": 1} and mdl._host_stale == {"W"}
+    w_host = mdl.__dict__["_W"]
+    np.testing.assert_array_equal(mdl.W, ctx.W.astype(np.float32).astype(np.float64))
+    assert mdl.__dict__["_W"] is not w_host and mdl.W.dtype == np.float64     # rebound
+    assert ctx.down == {"W": 1, "H": 1, "G": 1} and mdl._host_stale == set() and mdl._handed == {"G", "H", "W"}
+    mdl.factorize(niter=1)                                            # handed out, unchanged: digested, not uploaded
+    assert ctx.up == {"W": 0, "H": 0, "G": 0, "V": 1} and mdl._handed == set()
+    assert mdl._host_stale == {"G", "H", "W"} and ctx.down == {"W": 1, "H": 1, "G": 1}
+
+
+def test_cnmf_in_place_edit_of_g_reaches_the_device_and_setters_run_g_h_w():
+    mdl = _cnmf_with_double(seed=1)
+    ctx = mdl._ctx
+    mdl.factorize(niter=1)
+    mdl.G[0, 0] += 0.5                                                # read (refresh, in place) + edit
+    assert ctx.down["G"] == 1 and mdl._host_stale == {"H", "W"}
+    expect = mdl.__dict__["_G"].copy()
+    ctx.log[:] = []
+    mdl.factorize(niter=0)
+    assert ctx.log == ["set_g", "factorize(0)"], ctx.log               # H and W: the device copies are the newer ones
+    np.testing.assert_array_equal(ctx.G, expect)
+    assert mdl._host_stale == {"H", "W"}                              # no iteration ran: G's host array stays current
+    # all three assigned: G, H, W in that order (the library's w_replaced / h_replaced bookkeeping sees them so)
+    rs = np.random.RandomState(3)
+    mdl.W, mdl.H, mdl.G = rs.rand(20, 3), rs.rand(3, 10), rs.rand(10, 3)
+    assert mdl._host_stale == set() and mdl._g_fp is None and mdl._h_fp is None and mdl._w_fp is None
+    ctx.log[:] = []
+    mdl.factorize(niter=1, compute_w=False)
+    assert ctx.log == ["set_g", "set_h", "set_w", "factorize(1)"], ctx.log
+    assert mdl._host_stale == {"H"}                                   # compute_w=False: G and W did not move
+    ctx.log[:] = []
+    mdl.factorize(niter=1, compute_h=False)
+    assert ctx.log == ["factorize(1)"] and mdl._host_stale == {"G", "H", "W"}     # a W step moves W and G
+    mdl.G = np.arange(30).reshape(10, 3)
+    with pytest.raises(TypeError):
+        mdl.factorize(niter=1)                                        # an integer G, as an integer W in NMF
+
+
+def test_cnmf_factors_that_do_not_exist_yet_are_skipped_by_the_upload():
+    """init_h synchronises before H exists: a G the caller set goes up, what is missing is left to pmf_cnmf_init;
+    H and G given but no W: W = data G on the device."""
+    mdl = _cnmf_with_double(seed=2)
+    G0 = np.random.RandomState(4).rand(10, 3)
+    mdl.G = G0
+    mdl.factorize(niter=1)
+    assert mdl._ctx.log == ["set_v", "set_g", "cnmf_init", "factorize(1)"], mdl._ctx.log
+    # G0 is held by the caller: brought up to date in place, at once
+    assert mdl._host_stale == {"H", "W"} and mdl.__dict__["_G"] is G0 and mdl._ctx.down["G"] == 1
+    np.testing.assert_array_equal(G0, mdl._ctx.G)
+    m2 = _cnmf_with_double(seed=2)
+    m2.H, m2.G = np.ones((3, 10)), G0.copy()
+    m2.factorize(niter=0)
+    assert m2._ctx.log == ["set_v", "set_g", "set_h", "factorize(0)"], m2._ctx.log
+    assert m2._host_stale == {"W"} and m2._w_fp is None
+
+
+def test_cnmf_held_arrays_are_refreshed_after_every_call():
+    mdl = _cnmf_with_double(seed=5)
+    mdl.factorize(niter=1)
+    g, h = mdl.G, mdl.H
+    down = dict(mdl._ctx.down)
+    mdl.factorize(niter=2)
+    assert mdl.G is g and g[0, 0] == 3.01                             # in place
+    assert mdl.H is not h and h[0, 0] == 1.2 and mdl.H[0, 0] == 3.2   # rebound: the caller's old array is left alone
+    assert mdl._ctx.down == {"W": down["W"], "H": down["H"] + 1, "G": down["G"] + 1}
+    assert mdl._host_stale == {"W"}
+    mdl.eager_factors = True
+    mdl.factorize(niter=1, compute_h=False)
+    assert mdl._host_stale == set() and mdl._ctx.down == {"W": down["W"] + 1, "H": down["H"] + 1, "G": down["G"] + 2}
+
+
+def test_cnmf_pickle_and_copy_flush_all_three_factors():
+    import copy
+    import pickle
+    mdl = _cnmf_with_double(seed=6)
+    mdl.factorize(niter=2)
+    assert mdl._host_stale == {"G", "H", "W"}
+    clone = pickle.loads(pickle.dumps(mdl))
+    assert mdl._ctx.down == {"W": 1, "H": 1, "G": 1} and mdl._host_stale == set()
+    assert clone._ctx is None and clone._host_stale == set() and clone._handed == set()
+    assert clone._g_fp is None and clone._h_fp is None and clone._w_fp is None and clone._v_src is None
+    np.testing.assert_array_equal(clone.__dict__["_G"], mdl._ctx.G)
+    np.testing.assert_array_equal(clone.__dict__["_H"], mdl._ctx.H)
+    assert mdl._g_fp is not None and mdl._h_fp is not None and mdl._w_fp is not None
+    mdl.factorize(niter=1)
+    twin = copy.copy(mdl)
+    assert mdl._ctx.down == {"W": 2, "H": 2, "G": 2}
+    assert twin._host_stale is not mdl._host_stale and twin._handed is not mdl._handed
+    mdl.factorize(niter=1)                                            # stale again on the original only
+    assert twin._host_stale == set() and twin._ctx is None and twin._g_fp is None
+    assert mdl._ctx.up == {"W": 0, "H": 0, "G": 0, "V": 1}
+
+
+def test_cnmf_overridden_frobenius_norm_routes_through_the_hook_loop():
+    """An overridden frobenius_norm is called every iteration (cnmf.py:156-187): one device iteration per loop turn,
+    the factors staying on the device in between and afterwards."""
+    seen = []
+
+    class Mine(pymf_amd.CNMF):
+        def frobenius_norm(self):
+            seen.append(set(self._host_stale))
+            return 100.0 / len(seen)
+
+    mdl = _cnmf_with_double(seed=7, cls=Mine)
+    assert mdl._hooks_overridden() and not _cnmf_with_double()._hooks_overridden()
+    mdl.factorize(niter=3)
+    assert mdl._ctx.log == ["set_v", "cnmf_init", "factorize(1)", "factorize(1)", "factorize(1)"], mdl._ctx.log
+    assert seen == [{"G", "H", "W"}] * 3
+    np.testing.assert_allclose(mdl.ferr, [100.0, 50.0, 100.0 / 3])
+    assert mdl._host_stale == {"G", "H", "W"} and mdl._last_iters == 3
+    assert mdl._ctx.down == {"W": 0, "H": 0, "G": 0} and mdl._ctx.up == {"W": 0, "H": 0, "G": 0, "V": 1}
+    g = mdl.G
+    mdl._ctx.log[:] = []
+    mdl.factorize(niter=2, compute_h=False, compute_err=False)
+    assert mdl._ctx.log == ["factorize(1)", "factorize(1)"] and len(seen) == 3
+    assert mdl._ctx.down == {"W": 0, "H": 0, "G": 2}                  # the read, and one flush at the end of the loop
+    assert g[0, 0] == 5.01 and mdl._host_stale == {"H", "W"}
+    flat = _cnmf_with_double(seed=7)
+    flat.frobenius_norm = lambda: 7.0                                 # instance-level, constant: converged() cuts at i == 2
+    flat.factorize(niter=6)
+    assert flat._ctx.log[2:] == ["factorize(1)"] * 3 and len(flat.ferr) == 2 and flat._last_iters == 3
