@@ -36,6 +36,7 @@
  *   pmf_stream_*          the data[:,:] reads of       pymf/nmf.py:123,129 for data that is not resident
  *   pmf_cnmf_init         CNMF.init_h + Kmeans         pymf/cnmf.py:78-103, pymf/kmeans.py:64-87 (algo 5)
  *   pmf_set/get_g_f64     self.G of CNMF               pymf/cnmf.py:95-100
+ *   pmf_cluster_get/set_assigned  self.assigned of Kmeans  pymf/kmeans.py:77 (algo 6)
  *
  * Every function returns PMF_OK (0) or a negative status and never throws;
  * pmf_last_error() gives a human-readable message for the last failure.
@@ -60,7 +61,8 @@ enum {
   PMF_ESINGULAR = -5 /* SNMF: H H^T is singular (the reference's np.linalg.inv raises LinAlgError, snmf.py:69) */
 };
 
-enum { PMF_ALGO_NMF = 0, PMF_ALGO_NMFALS = 1, PMF_ALGO_SNMF = 2, PMF_ALGO_BNMF = 3, PMF_ALGO_RNMF = 4, PMF_ALGO_CNMF = 5 };
+enum { PMF_ALGO_NMF = 0, PMF_ALGO_NMFALS = 1, PMF_ALGO_SNMF = 2, PMF_ALGO_BNMF = 3, PMF_ALGO_RNMF = 4, PMF_ALGO_CNMF = 5,
+       PMF_ALGO_KMEANS = 6, PMF_ALGO_CMEANS = 8 };   /* 7 is not assigned: pmf_ctx_create refuses it */
 
 /* pmf_factorize flags (the reference's factorize() keyword arguments, nmf.py:141-142) */
 enum { PMF_COMPUTE_W = 1u, PMF_COMPUTE_H = 2u, PMF_COMPUTE_ERR = 4u };
@@ -199,6 +201,20 @@ int pmf_nndsvd_init(pmf_ctx* ctx, int32_t* rank_found);
 int pmf_cnmf_init(pmf_ctx* ctx, const int32_t* sel, int32_t km_niter, int32_t* assigned_out);
 int pmf_set_g_f64(pmf_ctx* ctx, const double* G);
 int pmf_get_g_f64(pmf_ctx* ctx, double* G);
+
+/* Kmeans (algo 6; pymf/kmeans.py) and Cmeans (algo 8; pymf/cmeans.py, fuzzifier m = 1.75): dense data, any m and n,
+ * num_bases <= 128, one rank -- pmf_ctx_create returns PMF_EINVAL otherwise.  One pass over V per iteration, spread over
+ * column panels of V (pmf_cluster.h); all cross-panel sums have a fixed order.  With these algos the common entry points mean:
+ *   pmf_update_h     Kmeans: assigned = argmin_j ||v_c - w_j|| (lowest index on ties), H one-hot (kmeans.py:75-79);
+ *                    Cmeans: H_jc = 1 / sum_i (d_jc / d_ic)^(2/(m-1)), d = ||v_c - w_j|| + 1e-8 (cmeans.py:71-81); needs V, W
+ *   pmf_update_w     Kmeans: centres with more than one member become the mean of their members (kmeans.py:82-87; needs an
+ *                    assignment: an H step, or pmf_cluster_set_assigned); Cmeans: W = V H^T / (rowsum(H) + 1e-8)
+ *   pmf_factorize    nmf.py:182-202: update_w, update_h, ||V - W H||, the convergence rule, under the PMF_COMPUTE_* flags
+ *   pmf_frobenius    the direct residual
+ * pmf_cluster_get_assigned: the n cluster indices of the last Kmeans H step (or the ones set); pmf_cluster_set_assigned: a
+ * caller's assignment (n indices in [0, num_bases)), which the next pmf_update_w uses. */
+int pmf_cluster_get_assigned(pmf_ctx* ctx, int32_t* assigned);
+int pmf_cluster_set_assigned(pmf_ctx* ctx, const int32_t* assigned);
 
 /* Device time (ms, HIP events on the library's stream) of the last pmf_factorize loop. */
 int pmf_last_loop_ms(pmf_ctx* ctx, double* ms);

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PMF_LIB") or os.path.join(_HERE, "csrc", "libpymf_hip.so")   # PMF_LIB: A/B builds
 
 PMF_OK, PMF_EINVAL, PMF_EHIP, PMF_ENCCL, PMF_ENOMEM, PMF_ESINGULAR = 0, -1, -2, -3, -4, -5
-ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF = 0, 1, 2, 3, 4, 5
+ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF, ALGO_KMEANS, ALGO_CMEANS = 0, 1, 2, 3, 4, 5, 6, 8   # (7: not assigned)
 COMPUTE_W, COMPUTE_H, COMPUTE_ERR = 1, 2, 4
 STREAM_RESID = 8
 NCCL_ID_BYTES = 128
@@ -63,6 +63,8 @@ SYMBOLS = [
     ("pmf_cnmf_init", _c.c_int, [_ctx, _c.c_void_p, _c.c_int32, _c.c_void_p]),
     ("pmf_set_g_f64", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_get_g_f64", _c.c_int, [_ctx, _c.c_void_p]),
+    ("pmf_cluster_get_assigned", _c.c_int, [_ctx, _c.c_void_p]),
+    ("pmf_cluster_set_assigned", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_stream_begin", _c.c_int, [_ctx, _c.c_uint32, _c.c_int64]),
     ("pmf_stream_tile", _c.c_int, [_ctx, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64]),
     ("pmf_stream_end", _c.c_int, [_ctx, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int32)]),
@@ -357,6 +359,17 @@ class Context(object):
         G = np.empty((self.n, self.k), dtype=np.float64)
         self._chk(self._lib.pmf_get_g_f64(self._h, G.ctypes.data))
         return G
+
+    def get_assigned(self):
+        """Kmeans: the cluster index of every sample (pmf_cluster_get_assigned)."""
+        out = np.empty(self.n, dtype=np.int32)
+        self._chk(self._lib.pmf_cluster_get_assigned(self._h, out.ctypes.data))
+        return out
+
+    def set_assigned(self, assigned):
+        a = np.ascontiguousarray(assigned, dtype=np.int32)
+        assert a.shape == (self.n,), (a.shape, self.n)
+        self._chk(self._lib.pmf_cluster_set_assigned(self._h, a.ctypes.data))
 
     def get_h64(self):
         H = np.empty((self.k, self.n), dtype=np.float64)

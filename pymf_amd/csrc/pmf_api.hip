@@ -35,6 +35,7 @@
 #include "pmf_nndsvd.h"
 #include "pmf_topk.h"
 #include "pmf_cnmf.h"
+#include "pmf_cluster.h"
 
 // the internal host code, by concern (each header: one anonymous-namespace block; the order is the dependency order)
 #include "pmf_host_ctx.h"
@@ -47,6 +48,7 @@
 #include "pmf_host_transport.h"
 #include "pmf_host_profile.h"
 #include "pmf_host_cnmf.h"
+#include "pmf_host_cluster.h"
 
 // =============================================================================================
 extern "C" {
@@ -72,13 +74,19 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                    int32_t rank, int32_t nranks, const void* nccl_id) {
   if (!out) return fail(nullptr, PMF_EINVAL, "out is NULL");
   *out = nullptr;
-  if (algo < 0 || algo > 5) return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF) or 5 (CNMF)");
+  if (algo < 0 || algo > 8 || algo == 7)
+    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans) or 8 (Cmeans)");
   if (m_local < 1 || n < 1 || k < 1) return fail(nullptr, PMF_EINVAL, "m, n, k must be >= 1");
   if (algo == PMF_ALGO_CNMF) {  // C = V^T V is n x n float64 (128 MiB at the limit); the k x k factors on one float64 MFMA tile row
     if (n > 4096) return fail(nullptr, PMF_EINVAL, "CNMF: n (samples) > 4096 is not supported by this build");
     if (k > 128) return fail(nullptr, PMF_EINVAL, "CNMF: num_bases > 128 is not supported by this build");
     if (k > n) return fail(nullptr, PMF_EINVAL, "CNMF: num_bases > n (the k-means initialisation samples num_bases columns)");
     if (nranks > 1) return fail(nullptr, PMF_EINVAL, "CNMF: one rank only in this build");
+  }
+  const bool cluster = algo == PMF_ALGO_KMEANS || algo == PMF_ALGO_CMEANS;
+  if (cluster) {                // k_cluster_pass holds one column's distances to all bases in the registers of four lanes
+    if (k > 128) return fail(nullptr, PMF_EINVAL, "Kmeans / Cmeans: num_bases > 128 is not supported by this build");
+    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "Kmeans / Cmeans: one rank only in this build");
   }
   // The reference has no limit on num_bases (nmf.py:116-120); the generic kernels beyond 128 bases have been checked against
   // the float64 oracles at 1 500, 2 304 and 2 432 bases (tests/sweeps/bigk_limit_probe.py, tests/test_gpu_bigk.py); beyond 2 432 (19 blocks of 128)
@@ -143,8 +151,10 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
     PMFCHK(dalloc(c, &c->dH, (size_t)c->KP * c->np));
     PMFCHK(dalloc(c, &c->dG, (size_t)c->KP * c->KP));
     PMFCHK(dalloc(c, &c->dGd, (size_t)c->KP * c->KP));
-    PMFCHK(dalloc(c, &c->dPS, (size_t)ps_elems(c)));
-    if (c->nb == 1) {
+    if (!cluster) PMFCHK(dalloc(c, &c->dPS, (size_t)ps_elems(c)));   // (Kmeans / Cmeans: no n-sized product buffers, pmf_cluster.h has its own)
+    if (cluster) {
+      PMFCHK(cluster_alloc(c));
+    } else if (c->nb == 1) {
       PMFCHK(dalloc(c, &c->dSlab, (size_t)nslabs * ps_elems(c)));
     } else {                    // one 128-base block at a time: [chunk][128][max(np, KP) + 128]
       PMFCHK(dalloc(c, &c->dSlab, (size_t)c->nchunks * 128 * (std::max(c->np, c->KP) + 128)));
@@ -161,7 +171,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
     c->ferr_cap = 4096;
     PMFCHK(dalloc(c, &c->dFerr, (size_t)c->ferr_cap));
     if (algo == PMF_ALGO_RNMF) PMFCHK(dalloc(c, &c->dD, (size_t)c->mp * c->np));
-    if (algo != PMF_ALGO_NMF && algo != PMF_ALGO_CNMF) {
+    if (algo != PMF_ALGO_NMF && algo != PMF_ALGO_CNMF && !cluster) {
       if (!c->dW1) PMFCHK(dalloc(c, &c->dW1, (size_t)std::max<int64_t>(c->mp, c->np) * c->KP));
       PMFCHK(dalloc(c, &c->dGinvT, (size_t)c->KP * c->KP));
     }
@@ -193,6 +203,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                                                                                                    : FUSED_NMF))
                                : std::string("tiled");
   if (algo == PMF_ALGO_CNMF) c->path = "cnmf_gram";
+  if (cluster) c->path = "cluster_panels";
   choose_stat_site(c, false);
   *out = c;
   return PMF_OK;
@@ -414,6 +425,12 @@ int pmf_get_h_f32(pmf_ctx* c, float* H) {
 
 int pmf_update_w(pmf_ctx* c) {
   if (c && c->algo == PMF_ALGO_CNMF) return PMF_OK;   // cnmf.py:70-76: both hooks are no-ops (the updates live in factorize)
+  if (c && is_cluster(c)) {                            // (the W step reads the assignment / H, not W: kmeans.py:82-87, cmeans.py:83-86)
+    PMFCHK(need(c, true, c->algo == PMF_ALGO_KMEANS, c->algo == PMF_ALGO_CMEANS));   // (Kmeans keeps the columns of centres with < 2 members)
+    PMFCHK(cluster_update_w(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMF_OK;
+  }
   PMFCHK(need(c, true, true, true));
   PMFCHK(do_update_w(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -422,6 +439,12 @@ int pmf_update_w(pmf_ctx* c) {
 }
 int pmf_update_h(pmf_ctx* c) {
   if (c && c->algo == PMF_ALGO_CNMF) return PMF_OK;
+  if (c && is_cluster(c)) {
+    PMFCHK(need(c, true, true, false));
+    PMFCHK(cluster_update_h(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMF_OK;
+  }
   PMFCHK(need(c, true, true, true));
   PMFCHK(do_update_h(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -434,12 +457,21 @@ int pmf_frobenius(pmf_ctx* c, double* out) {
     PMFCHK(cnmf_ready(c));
     return cnmf_error(c, false, out);
   }
+  if (is_cluster(c)) return frobenius_direct(c, out);
   PMFCHK(do_frobenius(c, out));
   return ipc_check(c);
 }
 
 int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, double* ferr,
                   int32_t* iters_done, int32_t* converged_at) {
+  if (c && is_cluster(c)) {
+    PMFCHK(need(c, true, true, true));
+    if (niter < 0 || ((flags & PMF_COMPUTE_ERR) && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
+    if (iters_done) *iters_done = 0;
+    if (converged_at) *converged_at = -1;
+    return cluster_factorize(c, niter, flags & PMF_COMPUTE_W, flags & PMF_COMPUTE_H, flags & PMF_COMPUTE_ERR, conv_eps, ferr,
+                             iters_done, converged_at);
+  }
   PMFCHK(need(c, true, true, true));
   const bool cw = flags & PMF_COMPUTE_W, ch = flags & PMF_COMPUTE_H, ce = flags & PMF_COMPUTE_ERR;
   if (niter < 0 || (ce && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
@@ -631,6 +663,30 @@ int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, do
   return check_singular(c);
 }
 
+int pmf_cluster_get_assigned(pmf_ctx* c, int32_t* assigned) {
+  if (!c || !assigned) return fail(c, PMF_EINVAL, "pmf_cluster_get_assigned: bad arguments");
+  if (c->algo != PMF_ALGO_KMEANS) return fail(c, PMF_EINVAL, "pmf_cluster_get_assigned: Kmeans only");
+  if (!c->cl_have_asg) return fail(c, PMF_EINVAL, "pmf_cluster_get_assigned: no assignment yet (update_h has not run)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(assigned, c->dClAsg, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PMF_OK;
+}
+
+int pmf_cluster_set_assigned(pmf_ctx* c, const int32_t* assigned) {
+  if (!c || !assigned) return fail(c, PMF_EINVAL, "pmf_cluster_set_assigned: bad arguments");
+  if (c->algo != PMF_ALGO_KMEANS) return fail(c, PMF_EINVAL, "pmf_cluster_set_assigned: Kmeans only");
+  for (int64_t q = 0; q < c->n; ++q)
+    if (assigned[q] < 0 || assigned[q] >= c->k) return fail(c, PMF_EINVAL, "pmf_cluster_set_assigned: index out of range");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemsetAsync(c->dClAsg, 0xFF, (size_t)c->np * sizeof(int32_t), c->stream));   // pad columns: -1
+  HIPCHK(c, hipMemcpyAsync(c->dClAsg, assigned, (size_t)c->n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->cl_have_asg = true;
+  c->cl_sums_valid = false;
+  return PMF_OK;
+}
+
 int pmf_set_lambda(pmf_ctx* c, double lamb_w, double lamb_h) {
   if (!c) return PMF_EINVAL;
   if (c->algo != PMF_ALGO_BNMF && c->algo != PMF_ALGO_RNMF)
@@ -690,7 +746,7 @@ int pmf_rnmf_set_s_f32(pmf_ctx* c, const float* S) {
 int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (c) c->hd_synced = false;
   if (!c) return PMF_EINVAL;
-  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
+  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c))   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (!c->have_w || !c->have_h) return fail(c, PMF_EINVAL, "pmf_stream_begin: W and H must be set");
   if (max_tile_rows < 1) return fail(c, PMF_EINVAL, "pmf_stream_begin: max_tile_rows must be >= 1");

@@ -1,0 +1,127 @@
+// pmf_host_cluster.h -- Kmeans / Cmeans: the one-pass iteration over column panels (kernels: pmf_cluster.h)
+// Host code of libpymf_hip.so: included by pmf_api.hip (the translation unit) in this order, nothing else includes it.
+#pragma once
+
+namespace {
+
+// The reference's iteration is update_w, then update_h (nmf.py:183-187): W from the assignment / memberships at hand, then
+// the new ones.  One launch of k_cluster_pass assigns with the current W and leaves the sums that the NEXT update_w divides
+// (cl_sums_valid); an update_w that no pass preceded (H from the caller, Cmeans' random H0) forms the sums alone first.
+inline bool is_cluster(const pmf_ctx* c) { return c->algo == PMF_ALGO_KMEANS || c->algo == PMF_ALGO_CMEANS; }
+
+int cluster_alloc(pmf_ctx* c) {
+  if (c->dClNum) return PMF_OK;
+  const int npanels = c->np / 64;
+  // a slab of mp x KP floats per workgroup: at most PMF_CL_MAX_WGS of them and 2 GiB in all (few, tall slabs when m >> n)
+  const int64_t by_mem = std::max<int64_t>(1, ((int64_t)1 << 31) / (c->mp * c->KP * (int64_t)sizeof(float)));
+  const int want = (int)std::min<int64_t>(std::min(npanels, PMF_CL_MAX_WGS), by_mem);
+  c->cl_ppw = (npanels + want - 1) / want;
+  c->cl_wgs = (npanels + c->cl_ppw - 1) / c->cl_ppw;
+  PMFCHK(dalloc(c, &c->dClNum, (size_t)c->cl_wgs * c->mp * c->KP));
+  PMFCHK(dalloc(c, &c->dClDen, (size_t)c->cl_wgs * c->KP));
+  PMFCHK(dalloc(c, &c->dClErr, (size_t)c->cl_wgs));
+  PMFCHK(dalloc(c, &c->dClWn, (size_t)c->KP));
+  PMFCHK(dalloc(c, &c->dClTot, (size_t)c->KP + 1));
+  PMFCHK(dalloc(c, &c->dClAsg, (size_t)c->np));
+  return PMF_OK;
+}
+
+template <int NT>
+int cluster_launch_t(pmf_ctx* c, const ClusterArgs& a) {
+  if (c->algo == PMF_ALGO_KMEANS)
+    hipLaunchKernelGGL((k_cluster_pass<NT, PMF_CL_KMEANS>), dim3((unsigned)c->cl_wgs), dim3(256), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL((k_cluster_pass<NT, PMF_CL_CMEANS>), dim3((unsigned)c->cl_wgs), dim3(256), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+// assign: the H step (assignment / memberships from the current W) with the sums; otherwise the sums alone
+int cluster_pass(pmf_ctx* c, bool assign) {
+  PMFCHK(cluster_alloc(c));
+  if (!assign && c->algo == PMF_ALGO_KMEANS && !c->cl_have_asg)
+    return fail(c, PMF_EINVAL, "Kmeans: update_w needs an assignment (update_h has not run)");
+  if (assign) {
+    hipLaunchKernelGGL(k_cluster_wnorm, dim3((unsigned)c->KP), dim3(256), 0, c->stream, c->dW, c->mp, c->KP, c->dClWn);
+    HIPCHK(c, hipGetLastError());
+  }
+  ClusterArgs a{};
+  a.V = c->dV; a.W = c->dW; a.H = c->dH; a.asg = c->dClAsg; a.wn = c->dClWn;
+  a.num = c->dClNum; a.den = c->dClDen; a.err = c->dClErr;
+  a.mp = c->mp; a.np = c->np; a.n = (int)c->n; a.k = c->k; a.npanels = c->np / 64; a.panels_per_wg = c->cl_ppw;
+  a.assign = assign ? 1 : 0;
+  a.expo = (float)(2.0 / (1.75 - 1.0));          // cmeans.py:73,79
+  stat_begin(c, SITE_CLUSTER);
+  switch (c->NT) {
+    case 1: PMFCHK(cluster_launch_t<1>(c, a)); break;
+    case 2: PMFCHK(cluster_launch_t<2>(c, a)); break;
+    case 4: PMFCHK(cluster_launch_t<4>(c, a)); break;
+    default: PMFCHK(cluster_launch_t<8>(c, a)); break;
+  }
+  stat_end(c, SITE_CLUSTER);
+  hipLaunchKernelGGL(k_cluster_totals, dim3(1), dim3(256), 0, c->stream, c->dClDen, c->dClErr, c->cl_wgs, c->KP, c->dClTot);
+  HIPCHK(c, hipGetLastError());
+  if (assign) {
+    h_replaced(c, false, true);
+    if (c->algo == PMF_ALGO_KMEANS) c->cl_have_asg = true;
+  }
+  c->cl_sums_valid = true;
+  c->cl_err_valid = assign && c->algo == PMF_ALGO_KMEANS;   // dClTot[KP] = ||V - W H||^2 of the W, H at hand
+  return PMF_OK;
+}
+
+int cluster_update_h(pmf_ctx* c) { return cluster_pass(c, true); }
+
+int cluster_update_w(pmf_ctx* c) {
+  if (!c->cl_sums_valid) PMFCHK(cluster_pass(c, false));
+  const int64_t elems = c->mp * c->KP;
+  const dim3 grid((unsigned)((elems + 255) / 256));
+  if (c->algo == PMF_ALGO_KMEANS)
+    hipLaunchKernelGGL(k_cluster_finish<PMF_CL_KMEANS>, grid, dim3(256), 0, c->stream, c->dClNum, c->cl_wgs, elems, c->KP, c->dClTot, c->dW);
+  else
+    hipLaunchKernelGGL(k_cluster_finish<PMF_CL_CMEANS>, grid, dim3(256), 0, c->stream, c->dClNum, c->cl_wgs, elems, c->KP, c->dClTot, c->dW);
+  HIPCHK(c, hipGetLastError());
+  w_replaced(c, false);
+  c->cl_err_valid = false;
+  return PMF_OK;
+}
+
+// ||V - W H||: Kmeans right behind its own assignment has it as sum_c min_j d^2; everything else takes the direct residual
+int cluster_error(pmf_ctx* c, double* out) {
+  if (!c->cl_err_valid) return frobenius_direct(c, out);
+  double e2 = 0.0;
+  HIPCHK(c, hipMemcpyAsync(&e2, c->dClTot + c->KP, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *out = std::sqrt(e2);
+  return PMF_OK;
+}
+
+// pmf_factorize for Kmeans / Cmeans: the loop of nmf.py:182-202
+int cluster_factorize(pmf_ctx* c, int32_t niter, bool cw, bool ch, bool ce, double conv_eps, double* ferr, int32_t* iters_done,
+                      int32_t* converged_at) {
+  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+  int done = 0;
+  for (int i = 0; i < niter; ++i) {
+    if (c->abort_flag.load(std::memory_order_relaxed) != 0) break;
+    if (cw) PMFCHK(cluster_update_w(c));
+    if (ch) PMFCHK(cluster_update_h(c));
+    ++done;
+    if (ce) {
+      PMFCHK(cluster_error(c, &ferr[i]));
+      if (i > 1 && std::fabs(ferr[i] - ferr[i - 1]) / (double)c->n < conv_eps) {   // nmf.py:134-139,198
+        if (converged_at) *converged_at = i;
+        break;
+      }
+    }
+  }
+  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  c->last_loop_ms = ms;
+  if (ce) for (int q = done; q < niter; ++q) ferr[q] = 0.0;
+  if (iters_done) *iters_done = done;
+  return PMF_OK;
+}
+
+}  // namespace

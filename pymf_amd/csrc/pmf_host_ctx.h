@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER };
 
 struct KernelStat {
   std::string name = "none";
@@ -151,6 +151,15 @@ struct pmf_ctx {
   bool cn_l_valid = false;      // dCnLA / dCnLB belong to the current G and C.  <- G, V (as above)
   bool cn_user_w = false;       // W was uploaded by the caller (not V G): the error is the direct residual with it.  <- W from the caller
   double cn_trc = 0.0;          // tr(C) of the current C
+  // Kmeans / Cmeans (pmf_cluster.h): per-workgroup slabs of V H^T, of the denominators and of the error, ||w_j||^2, their
+  // totals ([KP] denominators, then sum_c min_j d^2), the assignment
+  float* dClNum = nullptr;
+  double *dClDen = nullptr, *dClErr = nullptr, *dClWn = nullptr, *dClTot = nullptr;
+  int* dClAsg = nullptr;
+  int cl_wgs = 0, cl_ppw = 0;   // workgroups of k_cluster_pass, 64-column panels each owns
+  bool cl_have_asg = false;     // dClAsg holds an assignment (Kmeans: an H step ran, or pmf_cluster_set_assigned)
+  bool cl_sums_valid = false;   // the slabs belong to the current V and assignment (Kmeans) / H (Cmeans).  <- V, H (Cmeans), the assignment
+  bool cl_err_valid = false;    // dClTot[KP] = ||V - W H||^2 of the current V, W, H (Kmeans, right behind its H step).  <- V, W, H
   double lamb_w = 0.0, lamb_h = 0.0;   // BNMF penalty weights (bnmf.py:84-85,118-119)
   // streamed V (pmf_stream_*): row tiles pass through two device buffers, V is never resident
   float* dTile[2] = {nullptr, nullptr};
@@ -349,15 +358,21 @@ int need(pmf_ctx* c, bool v, bool w, bool h) {
 
 // ---- an operand came from outside: the "<-" table at the flags' declarations (pmf_ctx) written as code.  Every entry point that
 // replaces V, W, H or CNMF's G calls one of these instead of writing flags; the transitions inside the algorithms stay where they happen.
-void v_replaced(pmf_ctx* c) { c->vnorm_valid = c->vnorm_local_valid = c->ps_valid = c->num_valid = c->trace_ready = c->c_valid = false; }
+void v_replaced(pmf_ctx* c) {
+  c->vnorm_valid = c->vnorm_local_valid = c->ps_valid = c->num_valid = c->trace_ready = c->c_valid = false;
+  c->cl_sums_valid = c->cl_err_valid = false;
+}
 void w_replaced(pmf_ctx* c, bool by_caller) {   // by_caller: uploaded or filled through the ABI (not the NNDSVD init, not a restored snapshot)
   c->have_w = true; c->ps_valid = c->num_valid = c->trace_ready = c->w_implicit = false;
+  c->cl_err_valid = false;
   if (by_caller) c->cn_user_w = c->algo == PMF_ALGO_CNMF;   // (CNMF: the error is taken against this W until a G step rebinds it)
 }
 // hd_synced, hd_force: what the float64 H (SNMF, CNMF) is to the new float32 H -- written with it (true, false), the caller's float64
 // values beside their rounding (false, false), or not written at all (false, true: all of it is widened at its next use)
 void h_replaced(pmf_ctx* c, bool hd_synced, bool hd_force) {
   c->have_h = true; c->g_valid = c->num_valid = c->trace_ready = false; c->g_parts = 0; c->hd_synced = hd_synced; c->hd_force = hd_force;
+  c->cl_err_valid = false;
+  if (c->algo == PMF_ALGO_CMEANS) c->cl_sums_valid = false;   // (Kmeans' sums follow the assignment, not H: kmeans.py:82-87)
 }
 void g_replaced(pmf_ctx* c) {        // CNMF
   c->have_g = true; c->cn_ab_valid = c->cn_l_valid = false;

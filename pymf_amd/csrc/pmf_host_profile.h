@@ -13,7 +13,13 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
   const int old_site = st.site;
   st.site = SITE_NONE; st.name = "none"; st.flops = st.bytes = st.exec_flops = 0.0;
   char buf[96];
-  if (c->algo == PMF_ALGO_SNMF && gram) {
+  if (c->algo == PMF_ALGO_KMEANS || c->algo == PMF_ALGO_CMEANS) {
+    st.site = SITE_CLUSTER;
+    snprintf(buf, sizeof(buf), "k_cluster_pass<%d,%s>", c->NT, c->algo == PMF_ALGO_KMEANS ? "kmeans" : "cmeans");
+    st.name = buf;
+    st.flops = st.exec_flops = 4.0 * m * n * k;                  // W^T V and V H^T
+    st.bytes = 4.0 * (m * n + k * n + 2.0 * m * k);              // V once, H written, W read, the sums written
+  } else if (c->algo == PMF_ALGO_SNMF && gram) {
     st.site = SITE_MATERIALIZE;                   // the only m-sized kernel of a Gram-space loop: W = V M, once
     if (use_csr(c)) {
       st.name = "k_csr_w_blocks(W = V M)";
