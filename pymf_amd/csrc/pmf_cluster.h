@@ -3,14 +3,17 @@
 // Clustering data are wide (many samples = columns, few dimensions = rows), so a workgroup owns a contiguous range of
 // 64-column panels of V [mp][np] (a wave: 16 columns of each) and, per iteration (k_cluster_pass),
 //   A  for each of its panels: P = W^T V_panel on the fp32 MFMA (64-row tiles of W staged in LDS, V read from global, a panel
-//      row being one contiguous segment), ||v_c||^2 on the way; d^2 = ||w_j||^2 - 2 P_jc + ||v_c||^2 clamped at 0 (float64);
+//      row being one contiguous segment), ||v_c||^2 on the way; d^2 = ||w_j||^2 - 2 P_jc + ||v_c||^2 clamped at 0 (float64).
+//      The expansion cancels where d^2 << ||v||^2, so w and v are both taken relative to mu = the row means of V (fp32,
+//      k_cluster_rowmean; a distance does not change under a translation): subtracted from W as it is staged, from V as it
+//      is loaded, and ||w_j - mu||^2 is what k_cluster_wnorm forms.  Data far from the origin then cost no digits;
 //      Kmeans: argmin_j (lowest index on ties) -> assigned, one-hot H column; Cmeans: H_jc = d_j^-e / sum_i d_i^-e with
 //      d = sqrt(d^2) + 1e-8, e = 2 / (m - 1) = 8/3 (cmeans.py:73-81); denominators (member counts / row sums of H) and
 //      Kmeans' error sum_c min_j d^2 accumulated in float64;
 //   B  for each 64-row tile: Num = V_tile H_range^T on the MFMA over ALL its columns, written once into the workgroup's slab.
 // k_cluster_totals / k_cluster_finish add the slabs up in a fixed order in float64 and divide (kmeans.py:83-87,
 // cmeans.py:83-86): no float atomics anywhere, two runs give the same bits.  assign = 0 skips the MFMA of A and takes H (Cmeans)
-// or the assignment (Kmeans) as it is: the sums for an update_w() that no pass preceded.
+// or the assignment (Kmeans) as it is: the sums for an update_w() that no pass preceded.  B and the sums keep the untranslated V.
 #pragma once
 #include "pmf_dev.h"
 
@@ -20,24 +23,44 @@ constexpr int PMF_CL_MAX_WGS = 1024;
 struct ClusterArgs {
   const float* V;       // [mp][np]
   const float* W;       // [mp][KP]
+  const float* mu;      // [mp] row means of V
   float* H;             // [KP][np]
   int* asg;             // [np] (Kmeans; -1 in the pad columns)
-  const double* wn;     // [KP] ||w_j||^2
+  const double* wn;     // [KP] ||w_j - mu||^2
   float* num;           // [wgs][mp][KP]
   double* den;          // [wgs][KP]
-  double* err;          // [wgs]
+  double* err;          // [wgs][2]: sum_c min_j d^2, sum_c ||v_c - mu||^2 (Kmeans)
   int64_t mp;
   int np, n, k, npanels, panels_per_wg, assign;
   float expo;           // Cmeans: 2 / (m - 1)
 };
 
-// ||w_j||^2 in float64, one workgroup per basis
-__global__ __launch_bounds__(256) void k_cluster_wnorm(const float* __restrict__ W, int64_t mp, int KP, double* __restrict__ wn) {
+// mu[r] = mean over the n samples of V[r][.] (pad columns are zero): float64 sum in a fixed order, one workgroup per row
+__global__ __launch_bounds__(256) void k_cluster_rowmean(const float* __restrict__ V, int64_t np, int n, float* __restrict__ mu) {
+  __shared__ double part[256];
+  const float* row = V + (int64_t)blockIdx.x * np;
+  double s = 0.0;
+  for (int64_t q = threadIdx.x; q < np / 4; q += 256) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * q);
+    s += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);
+  }
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) mu[blockIdx.x] = (float)(part[0] / (double)n);
+}
+
+// ||w_j - mu||^2 in float64 (the difference in fp32, as k_cluster_pass stages it), one workgroup per basis
+__global__ __launch_bounds__(256) void k_cluster_wnorm(const float* __restrict__ W, const float* __restrict__ mu, int64_t mp, int KP,
+                                                       double* __restrict__ wn) {
   __shared__ double part[256];
   const int j = blockIdx.x;
   double s = 0.0;
   for (int64_t r = threadIdx.x; r < mp; r += 256) {
-    const double w = (double)W[r * KP + j];
+    const double w = (double)(W[r * KP + j] - mu[r]);
     s = fma(w, w, s);
   }
   part[threadIdx.x] = s;
@@ -54,15 +77,16 @@ __global__ __launch_bounds__(256) void k_cluster_pass(const ClusterArgs a) {
   constexpr int KP = 16 * NT;
   constexpr int LW = KP == 16 ? 16 : KP + 16;   // row stride = 16 mod 64 floats: the 4 rows of an A fragment on 4 x 16 different banks
   __shared__ float wt[64 * LW];
+  __shared__ float smu[64];
   __shared__ double sden[4][KP];
-  __shared__ double serr[4];
+  __shared__ double serr[4][2];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lg = lane >> 4;
   const int p0 = blockIdx.x * a.panels_per_wg, p1 = min(p0 + a.panels_per_wg, a.npanels);
   const int ntiles = (int)(a.mp / 64);
   const int64_t np = a.np;
 
   double den[NT][4], wnr[NT][4];
-  double err = 0.0;
+  double err = 0.0, vsum = 0.0;
 #pragma unroll
   for (int jt = 0; jt < NT; ++jt)
 #pragma unroll
@@ -85,16 +109,22 @@ __global__ __launch_bounds__(256) void k_cluster_pass(const ClusterArgs a) {
         if (ntiles > 1 || p == p0) {             // (a W of one tile is staged once per workgroup)
           __syncthreads();
           const float* wsrc = a.W + (int64_t)rt * 64 * KP;
+          const float* msrc = a.mu + (int64_t)rt * 64;
           for (int q = tid; q < 64 * (KP / 4); q += 256) {
             const int row = q / (KP / 4), ch = q % (KP / 4);
-            *reinterpret_cast<f32x4*>(wt + row * LW + 4 * ch) = *reinterpret_cast<const f32x4*>(wsrc + row * KP + 4 * ch);
+            const float mr = msrc[row];
+            f32x4 w = *reinterpret_cast<const f32x4*>(wsrc + row * KP + 4 * ch);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w[e] -= mr;
+            *reinterpret_cast<f32x4*>(wt + row * LW + 4 * ch) = w;
           }
+          if (tid < 64) smu[tid] = msrc[tid];
           __syncthreads();
         }
         const float* vp = a.V + ((int64_t)rt * 64 + lg) * np + c;
 #pragma unroll 4
         for (int s = 0; s < 16; ++s) {           // rows 4 s + lg: A = W[row][16 jt + lc], B = V[row][c]
-          const float v = vp[(int64_t)(4 * s) * np];
+          const float v = vp[(int64_t)(4 * s) * np] - smu[4 * s + lg];
           vn = fmaf(v, v, vn);
           const float* wl = wt + (4 * s + lg) * LW + lc;
 #pragma unroll
@@ -132,7 +162,7 @@ __global__ __launch_bounds__(256) void k_cluster_pass(const ClusterArgs a) {
           for (int r = 0; r < 4; ++r) hv[jt][r] = (valid && jt * 16 + 4 * lg + r == bj) ? 1.f : 0.f;
         if (lg == 0) {
           a.asg[c] = valid ? bj : -1;
-          if (valid) err += bd;
+          if (valid) { err += bd; vsum += (double)vn; }
         }
       } else {
         float df[NT][4];
@@ -194,11 +224,14 @@ __global__ __launch_bounds__(256) void k_cluster_pass(const ClusterArgs a) {
       if (lc == 0) sden[wave][jt * 16 + 4 * lg + r] = s;
     }
 #pragma unroll
-  for (int x = 1; x <= 8; x <<= 1) err += __shfl_xor(err, x);
-  if (lane == 0) serr[wave] = err;
+  for (int x = 1; x <= 8; x <<= 1) {
+    err += __shfl_xor(err, x);
+    vsum += __shfl_xor(vsum, x);
+  }
+  if (lane == 0) { serr[wave][0] = err; serr[wave][1] = vsum; }
   __syncthreads();                               // (also: this workgroup's H / asg writes are visible to all its waves)
   if (tid < KP) a.den[(int64_t)blockIdx.x * KP + tid] = (sden[0][tid] + sden[1][tid]) + (sden[2][tid] + sden[3][tid]);
-  if (tid == 0) a.err[blockIdx.x] = (serr[0] + serr[1]) + (serr[2] + serr[3]);
+  if (tid < 2) a.err[2 * (int64_t)blockIdx.x + tid] = (serr[0][tid] + serr[1][tid]) + (serr[2][tid] + serr[3][tid]);
 
   // ---- B: Num[row][j] = sum_c V[row][c] H[j][c] over the workgroup's columns ------------------------------------------
   // A = V[r0 + lc][c0 + 4 lg + e], B = H[16 jt + lc][c0 + 4 lg + e]: one 16-byte read feeds 4 MFMAs (k order is free)
@@ -236,7 +269,7 @@ __global__ __launch_bounds__(256) void k_cluster_pass(const ClusterArgs a) {
   }
 }
 
-// tot[0 .. KP) = denominators, tot[KP] = sum_c min_j d^2: the workgroups' partials in order
+// tot[0 .. KP) = denominators, tot[KP] = sum_c min_j d^2, tot[KP + 1] = sum_c ||v_c - mu||^2: the workgroups' partials in order
 __global__ __launch_bounds__(256) void k_cluster_totals(const double* __restrict__ den, const double* __restrict__ err, int wgs, int KP,
                                                         double* __restrict__ tot) {
   const int t = threadIdx.x;
@@ -244,10 +277,10 @@ __global__ __launch_bounds__(256) void k_cluster_totals(const double* __restrict
     double s = 0.0;
     for (int g = 0; g < wgs; ++g) s += den[(int64_t)g * KP + t];
     tot[t] = s;
-  } else if (t == KP) {
+  } else if (t < KP + 2) {
     double s = 0.0;
-    for (int g = 0; g < wgs; ++g) s += err[g];
-    tot[KP] = s;
+    for (int g = 0; g < wgs; ++g) s += err[2 * (int64_t)g + (t - KP)];
+    tot[t] = s;
   }
 }
 

@@ -19,9 +19,10 @@ int cluster_alloc(pmf_ctx* c) {
   c->cl_wgs = (npanels + c->cl_ppw - 1) / c->cl_ppw;
   PMFCHK(dalloc(c, &c->dClNum, (size_t)c->cl_wgs * c->mp * c->KP));
   PMFCHK(dalloc(c, &c->dClDen, (size_t)c->cl_wgs * c->KP));
-  PMFCHK(dalloc(c, &c->dClErr, (size_t)c->cl_wgs));
+  PMFCHK(dalloc(c, &c->dClErr, (size_t)c->cl_wgs * 2));
   PMFCHK(dalloc(c, &c->dClWn, (size_t)c->KP));
-  PMFCHK(dalloc(c, &c->dClTot, (size_t)c->KP + 1));
+  PMFCHK(dalloc(c, &c->dClTot, (size_t)c->KP + 2));
+  PMFCHK(dalloc(c, &c->dClMu, (size_t)c->mp));
   PMFCHK(dalloc(c, &c->dClAsg, (size_t)c->np));
   return PMF_OK;
 }
@@ -42,11 +43,16 @@ int cluster_pass(pmf_ctx* c, bool assign) {
   if (!assign && c->algo == PMF_ALGO_KMEANS && !c->cl_have_asg)
     return fail(c, PMF_EINVAL, "Kmeans: update_w needs an assignment (update_h has not run)");
   if (assign) {
-    hipLaunchKernelGGL(k_cluster_wnorm, dim3((unsigned)c->KP), dim3(256), 0, c->stream, c->dW, c->mp, c->KP, c->dClWn);
+    if (!c->cl_mu_valid) {                         // once per uploaded V
+      hipLaunchKernelGGL(k_cluster_rowmean, dim3((unsigned)c->mp), dim3(256), 0, c->stream, c->dV, (int64_t)c->np, (int)c->n, c->dClMu);
+      HIPCHK(c, hipGetLastError());
+      c->cl_mu_valid = true;
+    }
+    hipLaunchKernelGGL(k_cluster_wnorm, dim3((unsigned)c->KP), dim3(256), 0, c->stream, c->dW, c->dClMu, c->mp, c->KP, c->dClWn);
     HIPCHK(c, hipGetLastError());
   }
   ClusterArgs a{};
-  a.V = c->dV; a.W = c->dW; a.H = c->dH; a.asg = c->dClAsg; a.wn = c->dClWn;
+  a.V = c->dV; a.W = c->dW; a.H = c->dH; a.mu = c->dClMu; a.asg = c->dClAsg; a.wn = c->dClWn;
   a.num = c->dClNum; a.den = c->dClDen; a.err = c->dClErr;
   a.mp = c->mp; a.np = c->np; a.n = (int)c->n; a.k = c->k; a.npanels = c->np / 64; a.panels_per_wg = c->cl_ppw;
   a.assign = assign ? 1 : 0;
@@ -86,13 +92,16 @@ int cluster_update_w(pmf_ctx* c) {
   return PMF_OK;
 }
 
-// ||V - W H||: Kmeans right behind its own assignment has it as sum_c min_j d^2; everything else takes the direct residual
+// ||V - W H||: Kmeans right behind its own assignment has it as sum_c min_j d^2, unless that is below 1e-3 of the centred
+// ||V - mu||^2 (tight clusters: the expansion has cancelled, the rule of nmf_error / cnmf_error); everything else takes
+// the direct residual
 int cluster_error(pmf_ctx* c, double* out) {
   if (!c->cl_err_valid) return frobenius_direct(c, out);
-  double e2 = 0.0;
-  HIPCHK(c, hipMemcpyAsync(&e2, c->dClTot + c->KP, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  double t[2] = {0.0, 0.0};                        // sum_c min_j d^2, sum_c ||v_c - mu||^2
+  HIPCHK(c, hipMemcpyAsync(t, c->dClTot + c->KP, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  *out = std::sqrt(e2);
+  if (!(t[0] > 1e-3 * t[1])) return frobenius_direct(c, out);
+  *out = std::sqrt(t[0]);
   return PMF_OK;
 }
 

@@ -151,14 +151,15 @@ struct pmf_ctx {
   bool cn_l_valid = false;      // dCnLA / dCnLB belong to the current G and C.  <- G, V (as above)
   bool cn_user_w = false;       // W was uploaded by the caller (not V G): the error is the direct residual with it.  <- W from the caller
   double cn_trc = 0.0;          // tr(C) of the current C
-  // Kmeans / Cmeans (pmf_cluster.h): per-workgroup slabs of V H^T, of the denominators and of the error, ||w_j||^2, their
-  // totals ([KP] denominators, then sum_c min_j d^2), the assignment
-  float* dClNum = nullptr;
+  // Kmeans / Cmeans (pmf_cluster.h): per-workgroup slabs of V H^T, of the denominators and of the error, ||w_j - mu||^2, their
+  // totals ([KP] denominators, then sum_c min_j d^2 and sum_c ||v_c - mu||^2), the assignment, mu = the row means of V
+  float *dClNum = nullptr, *dClMu = nullptr;
   double *dClDen = nullptr, *dClErr = nullptr, *dClWn = nullptr, *dClTot = nullptr;
   int* dClAsg = nullptr;
   int cl_wgs = 0, cl_ppw = 0;   // workgroups of k_cluster_pass, 64-column panels each owns
   bool cl_have_asg = false;     // dClAsg holds an assignment (Kmeans: an H step ran, or pmf_cluster_set_assigned)
   bool cl_sums_valid = false;   // the slabs belong to the current V and assignment (Kmeans) / H (Cmeans).  <- V, H (Cmeans), the assignment
+  bool cl_mu_valid = false;     // dClMu holds the row means of the current V.  <- V
   bool cl_err_valid = false;    // dClTot[KP] = ||V - W H||^2 of the current V, W, H (Kmeans, right behind its H step).  <- V, W, H
   double lamb_w = 0.0, lamb_h = 0.0;   // BNMF penalty weights (bnmf.py:84-85,118-119)
   // streamed V (pmf_stream_*): row tiles pass through two device buffers, V is never resident
@@ -360,7 +361,7 @@ int need(pmf_ctx* c, bool v, bool w, bool h) {
 // replaces V, W, H or CNMF's G calls one of these instead of writing flags; the transitions inside the algorithms stay where they happen.
 void v_replaced(pmf_ctx* c) {
   c->vnorm_valid = c->vnorm_local_valid = c->ps_valid = c->num_valid = c->trace_ready = c->c_valid = false;
-  c->cl_sums_valid = c->cl_err_valid = false;
+  c->cl_sums_valid = c->cl_err_valid = c->cl_mu_valid = false;
 }
 void w_replaced(pmf_ctx* c, bool by_caller) {   // by_caller: uploaded or filled through the ABI (not the NNDSVD init, not a restored snapshot)
   c->have_w = true; c->ps_valid = c->num_valid = c->trace_ready = c->w_implicit = false;
