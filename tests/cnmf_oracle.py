@@ -83,14 +83,17 @@ def cnmf_init(data, k, sel, G=None, km_niter=10, vq_fn=vq):
     return H, G, assigned
 
 
-def cnmf_factorize(data, H, G, W=None, niter=10, compute_w=True, compute_h=True, compute_err=True):
-    """CNMF.factorize (cnmf.py:108-187) from (H, G, W); W None: data G.  Returns (W, H, G, ferr)."""
+def cnmf_factorize(data, H, G, W=None, niter=10, compute_w=True, compute_h=True, compute_err=True, gram=None, w_round=None):
+    """CNMF.factorize (cnmf.py:108-187) from (H, G, W); W None: data G.  Returns (W, H, G, ferr).
+    gram: a matrix to stand in for data^T data; w_round: applied to W = data G wherever it is formed (both for
+    tests/cnmf_cases.py: what a float32 C and a float32 W cost whatever the arithmetic)."""
+    w_round = w_round or (lambda w: w)
     data = np.asarray(data, dtype=np.float64)
     H = np.array(H, dtype=np.float64)
     G = np.array(G, dtype=np.float64)
-    W = np.dot(data, G) if W is None else np.array(W, dtype=np.float64)   # cnmf.py:102-103
+    W = w_round(np.dot(data, G)) if W is None else np.array(W, dtype=np.float64)   # cnmf.py:102-103
     n = data.shape[1]
-    XtX = np.dot(data.T, data)                                       # cnmf.py:150
+    XtX = np.dot(data.T, data) if gram is None else np.asarray(gram, dtype=np.float64)   # cnmf.py:150
     XtX_pos, XtX_neg = _pos(XtX), _neg(XtX)                          # cnmf.py:151-152
     ferr = np.zeros(niter)                                           # cnmf.py:154
     for i in range(niter):
@@ -106,7 +109,7 @@ def cnmf_factorize(data, H, G, W=None, niter=10, compute_w=True, compute_h=True,
             wa = np.dot(XtX_pos, H.T) + np.dot(A, S)
             wb = np.dot(XtX_neg, H.T) + np.dot(B, S) + EPS_DEN
             G = G * np.sqrt(wa / wb)
-            W = np.dot(data, G)
+            W = w_round(np.dot(data, G))
         if compute_err:                                              # cnmf.py:177-179, frobenius_norm nmf.py:100-114
             ferr[i] = np.sqrt(np.sum((data - np.dot(W, H)) ** 2))
         if i > 1 and compute_err and _converged(ferr, i, n):        # cnmf.py:184-187

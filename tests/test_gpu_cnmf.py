@@ -10,6 +10,7 @@ import pytest
 
 from conftest import GOLDEN, close, load_golden, rel_fro
 import cnmf_oracle
+from cnmf_cases import planted as _planted
 
 pytestmark = pytest.mark.gpu
 
@@ -59,21 +60,6 @@ def test_factorize_matches_reference_golden(pm, name):
     Wref = d["W"] if "W" in d else d["V"].astype(np.float64).dot(d["G"])
     assert rel_fro(mdl.W, Wref, "mdl.W") < 2e-5
     close(mdl.ferr, d["ferr"], rtol=1e-5, what="mdl.ferr")
-
-
-def _planted(m, n, k, rseed, noise=0.05):
-    """Data with k well separated clusters of samples whose first members are exactly the samples random.sample draws
-    under random.seed(rseed): the k-means has no near-ties to decide."""
-    random.seed(rseed)
-    sel = np.sort(random.sample(range(n), k))
-    labels = np.arange(n) % k
-    rest = np.setdiff1d(np.arange(n), sel)
-    labels[sel] = np.arange(k)
-    labels[rest] = np.arange(len(rest)) % k
-    rs = np.random.RandomState(rseed)
-    centres = rs.random_sample((m, k))
-    V = centres[:, labels] + noise * rs.random_sample((m, n))
-    return V.astype(np.float32), sel, labels
 
 
 @pytest.mark.parametrize("m,n,k,niter", [(262144, 256, 32, 10), (4096, 1024, 128, 10)])
