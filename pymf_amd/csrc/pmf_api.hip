@@ -47,8 +47,10 @@
 #include "pmf_host_nmfals.h"
 #include "pmf_host_transport.h"
 #include "pmf_host_profile.h"
+#include "pmf_host_loop.h"
 #include "pmf_host_cnmf.h"
 #include "pmf_host_cluster.h"
+#include "pmf_host_factorize.h"
 
 // =============================================================================================
 extern "C" {
@@ -464,201 +466,21 @@ int pmf_frobenius(pmf_ctx* c, double* out) {
 
 int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, double* ferr,
                   int32_t* iters_done, int32_t* converged_at) {
-  if (c && is_cluster(c)) {
-    PMFCHK(need(c, true, true, true));
-    if (niter < 0 || ((flags & PMF_COMPUTE_ERR) && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
-    if (iters_done) *iters_done = 0;
-    if (converged_at) *converged_at = -1;
-    return cluster_factorize(c, niter, flags & PMF_COMPUTE_W, flags & PMF_COMPUTE_H, flags & PMF_COMPUTE_ERR, conv_eps, ferr,
-                             iters_done, converged_at);
-  }
   PMFCHK(need(c, true, true, true));
   const bool cw = flags & PMF_COMPUTE_W, ch = flags & PMF_COMPUTE_H, ce = flags & PMF_COMPUTE_ERR;
   if (niter < 0 || (ce && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
-  if (c->algo == PMF_ALGO_CNMF) {
-    if (iters_done) *iters_done = 0;
-    if (converged_at) *converged_at = -1;
-    return cnmf_factorize(c, niter, cw, ch, ce, conv_eps, ferr, iters_done, converged_at);
-  }
-  // every early (error) return below leaves no pipelined W = V M write in flight on the side stream: a caller that then
-  // re-uploads W must not see the stale product land on top of it
-  struct WPipeGuard {
-    pmf_ctx* c; bool ok = false;
-    ~WPipeGuard() {
-      if (ok || !c->w_stream) return;
-      (void)hipStreamSynchronize(c->w_stream);
-      c->ev_w_pending[0] = c->ev_w_pending[1] = false;
-    }
-  } wguard{c};
   if (iters_done) *iters_done = 0;
   if (converged_at) *converged_at = -1;
-  c->want_trace = ce;
-  c->fixed_h_loop = cw && !ch && niter > 1 && c->algo == PMF_ALGO_NMF;
-  const bool fused = cw && ch && c->fused_wgs > 0 && !use_csr(c) &&
-                     (c->algo == PMF_ALGO_NMF || c->algo == PMF_ALGO_SNMF || c->algo == PMF_ALGO_BNMF ||
-                      c->algo == PMF_ALGO_RNMF);
-  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  int done = 0;
-  // Free-running form of the loop (NMF on the fused kernel with the error on): after one
-  // iteration in the ordinary form, chunks of iterations are enqueued back to back; the error and
-  // the convergence test of nmf.py:134-139 run on the device (k_conv_check) and a raised stop flag
-  // turns every later launch of the chunk into a no-op, so the results are those of the ordinary
-  // loop while the host reads back once per chunk instead of once per iteration.
-  // ... and the fixed-basis loop (compute_w = False, nmf.py:56-65: coefficients for an existing basis):
-  // (W^T V | W^T W) is formed once, every further iteration is the H-step kernel alone
-  const bool h_only = !cw && ch && ce && c->nb == 1 && !use_csr(c) &&
-                      (c->algo == PMF_ALGO_NMF || c->algo == PMF_ALGO_BNMF);
-  // (a host transport for the cross-rank sums blocks on the host every iteration: nothing to free-run)
-  // SNMF with both updates on: the loop runs in Gram space (snmf_gram_iteration), W materialised at the end
-  const bool gram = cw && ch && snmf_gram_ok(c, niter);
-  if (gram) PMFCHK(ensure_vgram(c));
-  choose_stat_site(c, gram);
-  const bool can_free_run = ((((fused && c->algo != PMF_ALGO_RNMF) || (gram && !use_csr(c) && c->nb == 1)) && ce) || h_only) &&
-                            !(c->host_ar && !(c->ipc.nranks > 1 && (size_t)ps_elems(c) * sizeof(float) <= PMF_IPC_MAX_BYTES));   // NMF, BNMF, SNMF on the fused kernel
-  // (a host transport blocks on the host in every iteration -- nothing to free-run -- unless the per-iteration payload
-  //  (P | S) fits the one-shot IPC all-reduce in front of it)
-  constexpr int kHostIters = 1, kChunk = 32;
-  bool free_run = false;
-  for (int i = 0; i < niter; ++i) {                       // nmf.py:182
-    if (c->abort_flag.load(std::memory_order_relaxed) != 0) break;   // pmf_abort: the caller discards this run (iters_done says how far it got)
-    if (free_run) {
-      const int chunk = std::min(kChunk, niter - i);
-      c->stop_arg = c->dStop;
-      const double lamb_w0 = c->lamb_w, lamb_h0 = c->lamb_h;   // BNMF: every H step scales them (bnmf.py:84-85)
-      const unsigned ipc_seq0 = c->ipc_seq;
-      const long long fold_calls0 = c->fold_calls;
-      unsigned seq_after[kChunk];                           // the exchange counter behind iteration i + j
-      int lrc = PMF_OK;
-      for (int j = 0; j < chunk && lrc == PMF_OK; ++j) {
-        seq_after[j] = c->ipc_seq;                          // (overwritten below once the iteration is enqueued)
-        c->gram_partial_ok = (c->algo == PMF_ALGO_NMF || c->algo == PMF_ALGO_BNMF) && i + j + 1 < niter && !c->fused8;
-        if (h_only) {
-          lrc = ensure_ps(c);                               // current since the first iteration (W is fixed)
-          if (lrc == PMF_OK) lrc = h_step_from_ps(c);
-        } else {
-          lrc = gram ? snmf_gram_iteration(c) : c->algo == PMF_ALGO_SNMF ? snmf_fused_iteration(c) : nmf_fused_iteration(c);
-        }
-        const double* tt = c->dScal + 2;                  // k_nmf_h_gram left <P,H>, <S,G> there ...
-        int ntt = 1;
-        if (lrc == PMF_OK && c->trace_ready && c->trace_parts > 0) { tt = c->dT1part; ntt = c->trace_parts; }   // ... or as pairs
-        if (lrc == PMF_OK && !c->trace_ready) {           // SNMF: the H-step kernel does not form them
-          const int nb = c->np / 16;
-          lrc = launch_trace_terms(c);
-          hipLaunchKernelGGL(k_sum_pairs_f64, dim3(1), dim3(256), 0, c->stream, c->dPart, nb, c->dScal);
-          tt = c->dScal;
-        }
-        // the next launch of the chunk is a one-pass kernel: it evaluates this iteration's error and the
-        // convergence test in its prologue (FusedCtl) -- no launch of its own for them
-        const bool fold = fused && !c->fused8 && !h_only && j + 1 < chunk && c->algo != PMF_ALGO_SNMF;
-        if (lrc == PMF_OK && fold) {
-          c->conv_iter = i + j; c->conv_tt = tt; c->conv_ntt = ntt; c->conv_eps = conv_eps;
-        } else if (lrc == PMF_OK) {
-          hipLaunchKernelGGL(k_conv_check, dim3(1), dim3(64), 0, c->stream, tt, ntt, c->vnorm2, conv_eps,
-                             (double)c->n, i + j, c->dFerr, c->dStop);
-          if (hipGetLastError() != hipSuccess) lrc = fail(c, PMF_EHIP, "k_conv_check launch failed");
-        }
-        seq_after[j] = c->ipc_seq;
-      }
-      c->stop_arg = nullptr;
-      c->conv_iter = -1;
-      PMFCHK(lrc);
-      int hstop[2] = {0, -1};
-      HIPCHK(c, hipMemcpyAsync(hstop, c->dStop, sizeof(hstop), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(ferr + i, c->dFerr + i, (size_t)chunk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      if (hstop[0] == 0) {                                // the whole chunk ran
-        done += chunk;
-        i += chunk - 1;
-        continue;
-      }
-      // iterations i .. hstop[1] ran, the rest of the chunk were no-ops (with a communicator the
-      // all-reduces still ran on the stale (P | S): it no longer belongs to W)
-      const int s_it = hstop[1];
-      done += s_it - i + 1;
-      // The FOLDED exchanges behind the stop neither pushed nor waited (k_reduce_slabs_tiles / k_nmf_h_gram return on the
-      // flag), on every rank alike (H, and with it the stop, is bit-identical across ranks): take their sequence numbers back,
-      // so that the next exchange that really runs is the successor of the last one that did.  Counting the skipped ones
-      // broke the two-slot invariant of pmf_ipc.h (a rank is at most one exchange ahead of a peer BECAUSE it needs that
-      // peer's flags of exchange s + 1 before it can push s + 2 into the slot of s): after an odd number of skipped exchanges
-      // the next push could land in a slot a slower peer was still adding up (round-5 advisor).  k_ipc_allreduce launches
-      // run whatever the flag says, so a chunk that used those keeps its count.
-      if (c->fold_calls - fold_calls0 == (long long)(c->ipc_seq - ipc_seq0) && c->ipc_seq != ipc_seq0) {
-        const long long skipped = (long long)(c->ipc_seq - seq_after[s_it - i]);
-        c->ipc_seq = seq_after[s_it - i];
-        c->ipc_calls -= skipped; c->fold_calls -= skipped;
-      }
-      if (c->algo == PMF_ALGO_BNMF) {                     // only s_it - i + 1 H steps really ran
-        c->lamb_w = lamb_w0; c->lamb_h = lamb_h0;
-        for (int q = 0; q < s_it - i + 1; ++q) { c->lamb_w *= 1.1; c->lamb_h *= 1.1; }
-      }
-      if (c->algo == PMF_ALGO_NMF || c->algo == PMF_ALGO_BNMF) {
-        // the launches behind the stop were no-ops, but the host-side picture of where G lives was
-        // advanced by them: put it back to what iteration s_it's H step (the last that ran) left
-        const bool part = s_it + 1 < niter && !c->fused8;
-        c->g_parts = part ? std::min(c->np / 64, PMF_HGRAM_MAX_WGS) : 0;
-      }
-      c->trace_ready = false;
-      if (multi_rank(c)) { c->ps_valid = false; c->trace_ready = false; }
-      if (hstop[0] == 1) {                                // nmf.py:198-202
-        if (converged_at) *converged_at = s_it;
-        break;
-      }
-      // the trace identity cancels at iteration s_it: evaluate it directly and go on in the
-      // ordinary form, exactly what do_frobenius would have done
-      free_run = false;
-      i = s_it;
-      PMFCHK(frobenius_direct(c, &ferr[i]));
-    } else {
-      if (gram) {
-        PMFCHK(snmf_gram_iteration(c));                     // SNMF on k x n sized data (C = V^T V is at hand)
-      } else if (cw && ch && c->algo == PMF_ALGO_SNMF && csr_fused_ok(c)) {
-        PMFCHK(snmf_csr_fused_iteration(c));                // CSR: one pass over the rows
-      } else if (fused) {                                   // update_w + update_h, one pass over V
-        c->gram_partial_ok = (c->algo == PMF_ALGO_NMF || c->algo == PMF_ALGO_BNMF) && i + 1 < niter && !c->fused8;
-        PMFCHK(c->algo == PMF_ALGO_SNMF ? snmf_fused_iteration(c) : nmf_fused_iteration(c));
-      } else {
-        if (cw) PMFCHK(do_update_w(c));                     // nmf.py:183-184
-        if (ch) PMFCHK(do_update_h(c));                     // nmf.py:186-187
-      }
-      ++done;
-      if (ce && c->algo == PMF_ALGO_RNMF && ch) {           // update_s already summed (V - W H)^2
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        ferr[i] = std::sqrt(c->rnmf_err2);
-      } else if (ce) {
-        PMFCHK(do_frobenius(c, &ferr[i]));                  // nmf.py:189-190
-      }
-    }
-    if (ce) {
-      if (i > 1) {                                        // nmf.py:198
-        const double derr = std::fabs(ferr[i] - ferr[i - 1]) / (double)c->n;   // nmf.py:135
-        if (derr < conv_eps) {                            // nmf.py:136
-          if (converged_at) *converged_at = i;            // caller: ferr = ferr[:i] (nmf.py:201)
-          break;
-        }
-      }
-    }
-    if (can_free_run && !free_run && i + 1 >= kHostIters && niter - (i + 1) >= 2 && c->vnorm_valid &&
-        ferr[i] * ferr[i] > 1e-2 * c->vnorm2) {
-      // far from the cancellation threshold: hand the history to the device and let it run
-      PMFCHK(dgrow(c, &c->dFerr, &c->ferr_cap, niter));
-      if (!c->dStop) PMFCHK(dalloc(c, &c->dStop, 2));
-      HIPCHK(c, hipMemcpyAsync(c->dFerr, ferr, (size_t)(i + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemsetAsync(c->dStop, 0, 2 * sizeof(int), c->stream));
-      free_run = true;
-    }
+  if (is_cluster(c)) { ClusterLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
+  if (c->algo == PMF_ALGO_CNMF) {
+    PMFCHK(cnmf_ready(c));
+    CnmfLoopSteps s{cw, ch, niter};
+    return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at);
   }
-  c->want_trace = false;
-  c->fixed_h_loop = false;
-  c->gram_partial_ok = false;
-  PMFCHK(materialize_w(c));      // Gram-space SNMF loop: W = V M once, inside the timed loop region
-  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->last_loop_ms = ms;
-  if (ce) for (int q = done; q < niter; ++q) ferr[q] = 0.0;   // as np.zeros(niter) leaves them (nmf.py:179-180)
-  if (iters_done) *iters_done = done;
-  wguard.ok = true;              // (materialize_w above joined the side stream)
+  WPipeGuard wguard{c};
+  NmfLoopSteps s = nmf_loop_steps(c, niter, cw, ch, ce);
+  PMFCHK(factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at));
+  wguard.ok = true;              // (the loop's close joined the side stream)
   PMFCHK(ipc_check(c));
   return check_singular(c);
 }
@@ -1159,8 +981,6 @@ int pmf_host_checksum(const void* data, uint64_t nbytes, uint64_t* out2) {
   return PMF_OK;
 }
 
-// The caller changed V behind the library's back (a streamed `data` object was rebound or edited): forget
-// everything derived from it -- ||V||^2, (W^T V | W^T W), the cached V H^T.
 int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
   if (!c || !name) return PMF_EINVAL;
   if (std::strcmp(name, "force_tiled") == 0) {
@@ -1394,6 +1214,8 @@ const char* pmf_collective_name(pmf_ctx* c) {
   return s.c_str();
 }
 
+// The caller changed V behind the library's back (a streamed `data` object was rebound or edited): forget
+// everything derived from it -- ||V||^2, (W^T V | W^T W), the cached V H^T.
 int pmf_invalidate_v(pmf_ctx* c) {
   if (!c) return PMF_EINVAL;
   v_replaced(c);

@@ -105,32 +105,19 @@ int cluster_error(pmf_ctx* c, double* out) {
   return PMF_OK;
 }
 
-// pmf_factorize for Kmeans / Cmeans: the loop of nmf.py:182-202
-int cluster_factorize(pmf_ctx* c, int32_t niter, bool cw, bool ch, bool ce, double conv_eps, double* ferr, int32_t* iters_done,
-                      int32_t* converged_at) {
-  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  int done = 0;
-  for (int i = 0; i < niter; ++i) {
-    if (c->abort_flag.load(std::memory_order_relaxed) != 0) break;
+// pmf_factorize for Kmeans / Cmeans: the steps of the loop of nmf.py:182-202 (pmf_host_loop.h); no free-running form
+struct ClusterLoopSteps {
+  bool cw, ch;
+  int iterate(pmf_ctx* c, int) {
     if (cw) PMFCHK(cluster_update_w(c));
     if (ch) PMFCHK(cluster_update_h(c));
-    ++done;
-    if (ce) {
-      PMFCHK(cluster_error(c, &ferr[i]));
-      if (i > 1 && std::fabs(ferr[i] - ferr[i - 1]) / (double)c->n < conv_eps) {   // nmf.py:134-139,198
-        if (converged_at) *converged_at = i;
-        break;
-      }
-    }
+    return PMF_OK;
   }
-  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->last_loop_ms = ms;
-  if (ce) for (int q = done; q < niter; ++q) ferr[q] = 0.0;
-  if (iters_done) *iters_done = done;
-  return PMF_OK;
-}
+  int error(pmf_ctx* c, int, double* out) { return cluster_error(c, out); }
+  bool may_free_run(const pmf_ctx*, int, double) const { return false; }
+  int enqueue(pmf_ctx* c, int, int, int, double) { return fail(c, PMF_EINVAL, "Kmeans / Cmeans: no free-running loop"); }
+  void rewind(pmf_ctx*, int, int) {}
+  int close(pmf_ctx*) { return PMF_OK; }
+};
 
 }  // namespace

@@ -138,81 +138,23 @@ int cnmf_ready(pmf_ctx* c) {
   return ensure_hd(c);
 }
 
-// pmf_factorize for CNMF: the loop of cnmf.py:156-187.  With the error on and W = V G, chunks of iterations are enqueued back to
-// back and the error and the convergence test run on the device (k_conv_check, stop flag), as in the free-running loops of
-// pmf_factorize; near the cancellation threshold and with a caller's W the loop goes on iteration by iteration.
-int cnmf_factorize(pmf_ctx* c, int32_t niter, bool cw, bool ch, bool ce, double conv_eps, double* ferr, int32_t* iters_done,
-                   int32_t* converged_at) {
-  PMFCHK(cnmf_ready(c));
-  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  constexpr int kChunk = 32;
-  int done = 0;
-  bool free_run = false;
-  for (int i = 0; i < niter; ++i) {                         // cnmf.py:121
-    if (c->abort_flag.load(std::memory_order_relaxed) != 0) break;
-    bool s_fresh = false;
-    if (free_run) {
-      const int chunk = std::min(kChunk, niter - i);
-      c->stop_arg = c->dStop;
-      int lrc = PMF_OK;
-      for (int j = 0; j < chunk && lrc == PMF_OK; ++j) {
-        lrc = cnmf_iteration(c, cw, ch, &s_fresh);
-        if (lrc == PMF_OK) lrc = cnmf_err_terms(c, s_fresh);
-        if (lrc == PMF_OK) {
-          hipLaunchKernelGGL(k_conv_check, dim3(1), dim3(64), 0, c->stream, c->dCnTT, 1, c->cn_trc, conv_eps, (double)c->n, i + j,
-                             c->dFerr, c->dStop);
-          if (hipGetLastError() != hipSuccess) lrc = fail(c, PMF_EHIP, "k_conv_check launch failed");
-        }
-      }
-      c->stop_arg = nullptr;
-      PMFCHK(lrc);
-      int hstop[2] = {0, -1};
-      HIPCHK(c, hipMemcpyAsync(hstop, c->dStop, sizeof(hstop), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(ferr + i, c->dFerr + i, (size_t)chunk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      if (hstop[0] == 0) {
-        done += chunk;
-        i += chunk - 1;
-        continue;
-      }
-      const int s_it = hstop[1];                           // iterations i .. s_it ran, the rest of the chunk were no-ops
-      done += s_it - i + 1;
-      if (hstop[0] == 1) {                                 // cnmf.py:184-187
-        if (converged_at) *converged_at = s_it;
-        break;
-      }
-      free_run = false;                                    // the identity cancels at s_it: its error directly, then on by hand
-      i = s_it;
-      PMFCHK(frobenius_direct(c, &ferr[i]));
-    } else {
-      PMFCHK(cnmf_iteration(c, cw, ch, &s_fresh));
-      ++done;
-      if (ce) PMFCHK(cnmf_error(c, s_fresh, &ferr[i]));    // cnmf.py:150
-    }
-    if (ce && i > 1) {                                     // nmf.py:134-139
-      const double derr = std::fabs(ferr[i] - ferr[i - 1]) / (double)c->n;
-      if (derr < conv_eps) {
-        if (converged_at) *converged_at = i;
-        break;
-      }
-    }
-    if (ce && !free_run && !c->cn_user_w && niter - (i + 1) >= 2 && ferr[i] * ferr[i] > 1e-2 * c->cn_trc) {
-      PMFCHK(dgrow(c, &c->dFerr, &c->ferr_cap, niter));
-      HIPCHK(c, hipMemcpyAsync(c->dFerr, ferr, (size_t)(i + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemsetAsync(c->dStop, 0, 2 * sizeof(int), c->stream));
-      free_run = true;
-    }
+// pmf_factorize for CNMF: the steps of the loop of cnmf.py:156-187 (pmf_host_loop.h).  With the error on and W = V G the loop
+// free-runs; near the cancellation threshold and with a caller's W it goes on iteration by iteration.
+struct CnmfLoopSteps {
+  bool cw, ch;
+  int niter;
+  bool s_fresh = false;        // dSd holds H H^T of the H the last iteration ended with
+  int iterate(pmf_ctx* c, int) { return cnmf_iteration(c, cw, ch, &s_fresh); }   // cnmf.py:121
+  int error(pmf_ctx* c, int, double* out) { return cnmf_error(c, s_fresh, out); }   // cnmf.py:150
+  bool may_free_run(const pmf_ctx* c, int i, double f) const { return !c->cn_user_w && niter - (i + 1) >= 2 && f * f > 1e-2 * c->cn_trc; }
+  int enqueue(pmf_ctx* c, int i, int j, int, double conv_eps) {
+    PMFCHK(cnmf_iteration(c, cw, ch, &s_fresh));
+    PMFCHK(cnmf_err_terms(c, s_fresh));
+    return launch_conv_check(c, c->dCnTT, 1, c->cn_trc, conv_eps, i + j);
   }
-  PMFCHK(materialize_w(c));    // W = V G once, the W the reference holds after the loop
-  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->last_loop_ms = ms;
-  if (ce) for (int q = done; q < niter; ++q) ferr[q] = 0.0;   // np.zeros(niter), cnmf.py:154
-  if (iters_done) *iters_done = done;
-  return PMF_OK;
-}
+  void rewind(pmf_ctx*, int, int) {}                     // (the validity flags describe G and H, which the no-ops left alone)
+  int close(pmf_ctx* c) { return materialize_w(c); }     // W = V G once, the W the reference holds after the loop
+};
 
 // One pass of the Gram-space k-means: (C Z)^T = Z^T C, z^T C z, the assignment, the counts and the error of iteration `it`
 int kmeans_assign_pass(pmf_ctx* c, int it, double eps) {

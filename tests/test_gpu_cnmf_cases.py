@@ -1,7 +1,7 @@
 """pymf_amd.CNMF on the MI355X where tests/test_gpu_cnmf.py does not reach: every width of k_cnmf_mul_step at its lowest and
 highest k, ragged k and n (the zero rows k .. KP and columns n .. np of G^T, H, L_A, L_B and S), mixed-sign data at every
 width (both halves of k_cnmf_split_gemm, the P2 / L2 chain), tiny m and n, the multi-row-block chunks of the dense V^T V,
-one step from a dense start, the chunk boundaries of cnmf_factorize, the stop state 2 of k_conv_check, loops without the
+one step from a dense start, the chunk boundaries of the CNMF loop of pmf_factorize, the stop state 2 of k_conv_check, loops without the
 error or without the G step, the k-means initialisation with one-member clusters, and data replaced under a live object.
 The cases and their float64 oracle results: tests/cnmf_cases.py; that they leave room for float32 and reach what they are
 meant for: tests/test_cnmf_cases.py.  Tolerances: DESIGN.md section 4 as in tests/test_gpu_cnmf.py -- 1e-5 relative
@@ -67,7 +67,7 @@ def test_one_step_from_a_dense_start(pm, r):
         assert np.array_equal(mdl.H, H0)
 
 
-# ---- 2: the paths of cnmf_factorize ---------------------------------------------------------------------------------------
+# ---- 2: the paths of the CNMF loop ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("r", cc.LOOP_RUNS + [cc.TWICE_RUN, cc.TWICE_EARLY_RUN], ids=cc.run_id)
 def test_chunk_boundaries(pm, r):
     """niter = 1, 2: by hand; 3: a chunk of two; 33, 34: a last chunk of 0 or 1 (by hand); 70: two chunks and one of five;

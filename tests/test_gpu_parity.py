@@ -541,22 +541,35 @@ def test_single_element_edit_is_noticed(pm):
     assert rel_fro(mdl.W, ref.W, what="mdl.W") < 6e-7 and rel_fro(mdl.H, ref.H, what="mdl.H") < 3e-7
 
 
-@pytest.mark.parametrize("algo_name", ["NMF", "SNMF", "BNMF"])
-def test_free_running_loop_matches_stepwise_loop(pm, algo_name):
+@pytest.mark.parametrize("algo_name,data", [("NMF", "random"), ("SNMF", "random"), ("BNMF", "random"), ("NMF", "low_rank")],
+                         ids=["NMF", "SNMF", "BNMF", "NMF-low_rank"])
+def test_free_running_loop_matches_stepwise_loop(pm, algo_name, data):
     """pmf_factorize enqueues chunks of iterations with the error and the convergence test of
     nmf.py:134-139 on the device; the outcome must be the one of the iteration-by-iteration loop
     (hooks + host-side test), including WHERE a convergence stops it (and, for BNMF, the penalty
-    weights the reference's schedule has reached by then)."""
+    weights the reference's schedule has reached by then).
+
+    low_rank: an exactly rank-3 V, whose trace identity cancels (error below 1e-3 of ||V||^2) in the MIDDLE of a chunk
+    -- stop state 2 of k_conv_check, the branch of the loop with the most host state to take back.  NMFOracle in
+    float64 on this input: ||V - W H||^2 / ||V||^2 = 0.043 after iteration 0 (above 1e-2: the loop hands over to the
+    device) and 1.087e-3, 0.990e-3, 0.903e-3 at iterations 69, 70, 71 -- inside the third chunk (65 .. 80)."""
     from pymf_amd import _lib
     algo = getattr(_lib, "ALGO_" + algo_name)
-    rs = np.random.RandomState(77)
-    m, n, k = 4096, 128, 16
-    V = rs.random_sample((m, n)).astype(np.float32)
+    if data == "low_rank":
+        rs = np.random.RandomState(5)
+        m, n, k = 300, 128, 3
+        V = (rs.random_sample((m, k)) @ rs.random_sample((k, n))).astype(np.float32)
+        runs = ((80, 0.0),)
+    else:
+        rs = np.random.RandomState(77)
+        m, n, k = 4096, 128, 16
+        V = rs.random_sample((m, n)).astype(np.float32)
+        runs = ((37, 1e-8), (60, 2e-5), (200, 1e-6))
     if algo_name == "BNMF":
         V = (V < 0.3).astype(np.float32)
     W0 = rs.random_sample((m, k)).astype(np.float32)
     H0 = rs.random_sample((k, n)).astype(np.float32)
-    for niter, eps in ((37, 1e-8), (60, 2e-5), (200, 1e-6)):
+    for niter, eps in runs:
         a = _lib.Context(algo, m, n, k)
         a.set_v_dense(V); a.set_w(W0); a.set_h(H0)
         if algo_name == "BNMF":
@@ -583,6 +596,13 @@ def test_free_running_loop_matches_stepwise_loop(pm, algo_name):
         np.testing.assert_array_equal(a.get_h(), b.get_h())
         if algo_name == "BNMF":
             assert a.get_lambda() == b.get_lambda()
+        if data == "low_rank":                           # the run did go through stop state 2, inside a chunk
+            assert a.path_name.startswith("k_nmf_fused")
+            vnorm2 = float(np.sum(V.astype(np.float64) ** 2))
+            below = np.nonzero(fa[:done_a] ** 2 < 1e-3 * vnorm2)[0]
+            print("low_rank: fa[0]^2 / ||V||^2 = %.4g, first index below 1e-3: %s" % (fa[0] ** 2 / vnorm2, below[:1]))
+            assert fa[0] ** 2 > 1e-2 * vnorm2
+            assert below.size and 65 < below[0] < 80, below[:1]
         # wherever the loop stopped, the context must be in a state the single hooks can go on from
         # (inside the loop G = H H^T lives as per-workgroup partial sums)
         a.update_w(); b.update_w()
