@@ -37,6 +37,7 @@
  *   pmf_cnmf_init         CNMF.init_h + Kmeans         pymf/cnmf.py:78-103, pymf/kmeans.py:64-87 (algo 5)
  *   pmf_set/get_g_f64     self.G of CNMF               pymf/cnmf.py:95-100
  *   pmf_cluster_get/set_assigned  self.assigned of Kmeans  pymf/kmeans.py:77 (algo 6)
+ *   pmf_sivm_get_select   self.select of SIVM          pymf/sivm.py:145-166,193 (algo 10)
  *
  * Every function returns PMF_OK (0) or a negative status and never throws;
  * pmf_last_error() gives a human-readable message for the last failure.
@@ -58,11 +59,12 @@ enum {
   PMF_EHIP = -2,     /* a HIP runtime call failed */
   PMF_ENCCL = -3,    /* an RCCL call failed */
   PMF_ENOMEM = -4,   /* device or host allocation failed */
-  PMF_ESINGULAR = -5 /* SNMF: H H^T is singular (the reference's np.linalg.inv raises LinAlgError, snmf.py:69) */
+  PMF_ESINGULAR = -5, /* SNMF: H H^T is singular (the reference's np.linalg.inv raises LinAlgError, snmf.py:69) */
+  PMF_ENUMERIC = -6   /* an iteration with a fixed cap of rounds did not finish (SIVM: the multiplier search of the H step) */
 };
 
 enum { PMF_ALGO_NMF = 0, PMF_ALGO_NMFALS = 1, PMF_ALGO_SNMF = 2, PMF_ALGO_BNMF = 3, PMF_ALGO_RNMF = 4, PMF_ALGO_CNMF = 5,
-       PMF_ALGO_KMEANS = 6, PMF_ALGO_CMEANS = 8 };   /* 7 is not assigned: pmf_ctx_create refuses it */
+       PMF_ALGO_KMEANS = 6, PMF_ALGO_CMEANS = 8, PMF_ALGO_SIVM = 10 };   /* 7 and 9 are not assigned: pmf_ctx_create refuses them */
 
 /* pmf_factorize flags (the reference's factorize() keyword arguments, nmf.py:141-142) */
 enum { PMF_COMPUTE_W = 1u, PMF_COMPUTE_H = 2u, PMF_COMPUTE_ERR = 4u };
@@ -215,6 +217,22 @@ int pmf_get_g_f64(pmf_ctx* ctx, double* G);
  * caller's assignment (n indices in [0, num_bases)), which the next pmf_update_w uses. */
 int pmf_cluster_get_assigned(pmf_ctx* ctx, int32_t* assigned);
 int pmf_cluster_set_assigned(pmf_ctx* ctx, const int32_t* assigned);
+
+/* SIVM (algo 10; pymf/sivm.py, simplex volume maximisation: W = num_bases selected columns of the data, the columns of H on the
+ * simplex): dense data, data_dimension <= 16384, num_bases <= 64, one rank -- pmf_ctx_create returns PMF_EINVAL otherwise.
+ * pmf_set_option "sivm_metric" (0 'l2' default, 1 'l1', 2 'cosine') and "sivm_init" (0 'fastmap' default, 1 'origin') carry the
+ * constructor's dist_measure and init.  With algo 10 the common entry points mean:
+ *   pmf_update_w     SIVM.update_w (sivm.py:145-201): num_bases + 2 ('fastmap') or num_bases ('origin') passes over V enqueued
+ *                    back to back (pmf_sivm.h), then W = V[:, select]; needs V only.  Two runs give the same bits.
+ *   pmf_update_h     AA.update_h (aa.py:93-111): per column min 1/2 x^T W^T W x - (W^T v)^T x, x >= 0, sum x = 1, as rounds of
+ *                    non-negative QPs with right-hand side W^T v + lambda and a bracketing secant on sum x(lambda) - 1; needs
+ *                    V, W.  PMF_EINVAL when W^T W is not positive definite (H is not unique: duplicate selected columns, or
+ *                    num_bases > data_dimension), PMF_ENUMERIC when a column is left with |sum x - 1| > 1e-6 after 48 rounds.
+ *   pmf_factorize    update_w, update_h, ||V - W H|| under the PMF_COMPUTE_* flags; the class always passes niter = 1
+ *   pmf_frobenius    the direct residual
+ * pmf_sivm_get_select: the num_bases selected column indices of the last pmf_update_w in selection order; under 'origin' the
+ * first is -1, which W treats as a Python index (the LAST data column, sivm.py:198). */
+int pmf_sivm_get_select(pmf_ctx* ctx, int32_t* select);
 
 /* Device time (ms, HIP events on the library's stream) of the last pmf_factorize loop. */
 int pmf_last_loop_ms(pmf_ctx* ctx, double* ms);

@@ -12,7 +12,8 @@ from .nndsvd import NNDSVD    # noqa: F401  (SURVEY 8(f) 'next' row 4)
 from .cnmf import CNMF        # noqa: F401  (convex NMF)
 from .kmeans import Kmeans    # noqa: F401  
 from .cmeans import Cmeans    # noqa: F401  
+from .sivm import SIVM        # noqa: F401  
 from . import dist            # noqa: F401
 
-__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "dist"]
+__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "dist"]
 __version__ = "0.1.0"

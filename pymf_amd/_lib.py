@@ -17,8 +17,8 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PMF_LIB") or os.path.join(_HERE, "csrc", "libpymf_hip.so")   # PMF_LIB: A/B builds
 
-PMF_OK, PMF_EINVAL, PMF_EHIP, PMF_ENCCL, PMF_ENOMEM, PMF_ESINGULAR = 0, -1, -2, -3, -4, -5
-ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF, ALGO_KMEANS, ALGO_CMEANS = 0, 1, 2, 3, 4, 5, 6, 8   # (7: not assigned)
+PMF_OK, PMF_EINVAL, PMF_EHIP, PMF_ENCCL, PMF_ENOMEM, PMF_ESINGULAR, PMF_ENUMERIC = 0, -1, -2, -3, -4, -5, -6
+ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF, ALGO_KMEANS, ALGO_CMEANS, ALGO_SIVM = 0, 1, 2, 3, 4, 5, 6, 8, 10   # (7, 9: not assigned)
 COMPUTE_W, COMPUTE_H, COMPUTE_ERR = 1, 2, 4
 STREAM_RESID = 8
 NCCL_ID_BYTES = 128
@@ -65,6 +65,7 @@ SYMBOLS = [
     ("pmf_get_g_f64", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_cluster_get_assigned", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_cluster_set_assigned", _c.c_int, [_ctx, _c.c_void_p]),
+    ("pmf_sivm_get_select", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_stream_begin", _c.c_int, [_ctx, _c.c_uint32, _c.c_int64]),
     ("pmf_stream_tile", _c.c_int, [_ctx, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64]),
     ("pmf_stream_end", _c.c_int, [_ctx, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int32)]),
@@ -370,6 +371,12 @@ class Context(object):
         a = np.ascontiguousarray(assigned, dtype=np.int32)
         assert a.shape == (self.n,), (a.shape, self.n)
         self._chk(self._lib.pmf_cluster_set_assigned(self._h, a.ctypes.data))
+
+    def get_select(self):
+        """SIVM: the selected column indices of the last update_w, in selection order (pmf_sivm_get_select)."""
+        out = np.empty(self.k, dtype=np.int32)
+        self._chk(self._lib.pmf_sivm_get_select(self._h, out.ctypes.data))
+        return out
 
     def get_h64(self):
         H = np.empty((self.k, self.n), dtype=np.float64)

@@ -36,6 +36,7 @@
 #include "pmf_topk.h"
 #include "pmf_cnmf.h"
 #include "pmf_cluster.h"
+#include "pmf_sivm.h"
 
 // the internal host code, by concern (each header: one anonymous-namespace block; the order is the dependency order)
 #include "pmf_host_ctx.h"
@@ -50,6 +51,7 @@
 #include "pmf_host_loop.h"
 #include "pmf_host_cnmf.h"
 #include "pmf_host_cluster.h"
+#include "pmf_host_sivm.h"
 #include "pmf_host_factorize.h"
 
 // =============================================================================================
@@ -76,8 +78,8 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                    int32_t rank, int32_t nranks, const void* nccl_id) {
   if (!out) return fail(nullptr, PMF_EINVAL, "out is NULL");
   *out = nullptr;
-  if (algo < 0 || algo > 8 || algo == 7)
-    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans) or 8 (Cmeans)");
+  if (algo < 0 || algo > 10 || algo == 7 || algo == 9)
+    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans), 8 (Cmeans) or 10 (SIVM)");
   if (m_local < 1 || n < 1 || k < 1) return fail(nullptr, PMF_EINVAL, "m, n, k must be >= 1");
   if (algo == PMF_ALGO_CNMF) {  // C = V^T V is n x n float64 (128 MiB at the limit); the k x k factors on one float64 MFMA tile row
     if (n > 4096) return fail(nullptr, PMF_EINVAL, "CNMF: n (samples) > 4096 is not supported by this build");
@@ -89,6 +91,11 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
   if (cluster) {                // k_cluster_pass holds one column's distances to all bases in the registers of four lanes
     if (k > 128) return fail(nullptr, PMF_EINVAL, "Kmeans / Cmeans: num_bases > 128 is not supported by this build");
     if (nranks > 1) return fail(nullptr, PMF_EINVAL, "Kmeans / Cmeans: one rank only in this build");
+  }
+  if (algo == PMF_ALGO_SIVM) {  // the H step's QPs run on the kernels of num_bases <= 64; k_sivm_pass stages one column of V in LDS
+    if (k > 64) return fail(nullptr, PMF_EINVAL, "SIVM: num_bases > 64 is not supported by this build");
+    if (m_local > PMF_SIVM_MAX_M) return fail(nullptr, PMF_EINVAL, "SIVM: data_dimension > 16384 is not supported by this build");
+    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "SIVM: one rank only in this build");
   }
   // The reference has no limit on num_bases (nmf.py:116-120); the generic kernels beyond 128 bases have been checked against
   // the float64 oracles at 1 500, 2 304 and 2 432 bases (tests/sweeps/bigk_limit_probe.py, tests/test_gpu_bigk.py); beyond 2 432 (19 blocks of 128)
@@ -206,6 +213,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                                : std::string("tiled");
   if (algo == PMF_ALGO_CNMF) c->path = "cnmf_gram";
   if (cluster) c->path = "cluster_panels";
+  if (algo == PMF_ALGO_SIVM) c->path = "sivm_panels";
   choose_stat_site(c, false);
   *out = c;
   return PMF_OK;
@@ -433,6 +441,13 @@ int pmf_update_w(pmf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
   }
+  if (c && c->algo == PMF_ALGO_SIVM) {                 // (the selection reads the data alone: sivm.py:145-201)
+    PMFCHK(need(c, true, false, false));
+    if (c->v_csr) return fail(c, PMF_EINVAL, "SIVM: dense data only");
+    PMFCHK(sivm_update_w(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMF_OK;
+  }
   PMFCHK(need(c, true, true, true));
   PMFCHK(do_update_w(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -444,6 +459,12 @@ int pmf_update_h(pmf_ctx* c) {
   if (c && is_cluster(c)) {
     PMFCHK(need(c, true, true, false));
     PMFCHK(cluster_update_h(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMF_OK;
+  }
+  if (c && c->algo == PMF_ALGO_SIVM) {
+    PMFCHK(need(c, true, true, false));
+    PMFCHK(sivm_update_h(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
   }
@@ -459,18 +480,20 @@ int pmf_frobenius(pmf_ctx* c, double* out) {
     PMFCHK(cnmf_ready(c));
     return cnmf_error(c, false, out);
   }
-  if (is_cluster(c)) return frobenius_direct(c, out);
+  if (is_cluster(c) || c->algo == PMF_ALGO_SIVM) return frobenius_direct(c, out);
   PMFCHK(do_frobenius(c, out));
   return ipc_check(c);
 }
 
 int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, double* ferr,
                   int32_t* iters_done, int32_t* converged_at) {
-  PMFCHK(need(c, true, true, true));
   const bool cw = flags & PMF_COMPUTE_W, ch = flags & PMF_COMPUTE_H, ce = flags & PMF_COMPUTE_ERR;
+  if (c && c->algo == PMF_ALGO_SIVM) PMFCHK(need(c, true, !cw, !ch));   // (either step writes its factor from scratch)
+  else PMFCHK(need(c, true, true, true));
   if (niter < 0 || (ce && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
   if (iters_done) *iters_done = 0;
   if (converged_at) *converged_at = -1;
+  if (c->algo == PMF_ALGO_SIVM) { SivmLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
   if (is_cluster(c)) { ClusterLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
   if (c->algo == PMF_ALGO_CNMF) {
     PMFCHK(cnmf_ready(c));
@@ -491,6 +514,16 @@ int pmf_cluster_get_assigned(pmf_ctx* c, int32_t* assigned) {
   if (!c->cl_have_asg) return fail(c, PMF_EINVAL, "pmf_cluster_get_assigned: no assignment yet (update_h has not run)");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(assigned, c->dClAsg, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PMF_OK;
+}
+
+int pmf_sivm_get_select(pmf_ctx* c, int32_t* select) {
+  if (!c || !select) return fail(c, PMF_EINVAL, "pmf_sivm_get_select: bad arguments");
+  if (c->algo != PMF_ALGO_SIVM) return fail(c, PMF_EINVAL, "pmf_sivm_get_select: SIVM only");
+  if (!c->sv_have_select) return fail(c, PMF_EINVAL, "pmf_sivm_get_select: no selection yet (update_w has not run)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(select, c->dSvSel, (size_t)c->k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return PMF_OK;
 }
@@ -568,7 +601,7 @@ int pmf_rnmf_set_s_f32(pmf_ctx* c, const float* S) {
 int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (c) c->hd_synced = false;
   if (!c) return PMF_EINVAL;
-  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c))   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
+  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c) || c->algo == PMF_ALGO_SIVM)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (!c->have_w || !c->have_h) return fail(c, PMF_EINVAL, "pmf_stream_begin: W and H must be set");
   if (max_tile_rows < 1) return fail(c, PMF_EINVAL, "pmf_stream_begin: max_tile_rows must be >= 1");
@@ -1056,6 +1089,18 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
   if (std::strcmp(name, "rowgemm_stream") == 0) {
     if (value != 0 && value != 1) return fail(c, PMF_EINVAL, "rowgemm_stream: 0 or 1");
     c->opt_rowgemm_stream = (int)value;
+    return PMF_OK;
+  }
+  if (std::strcmp(name, "sivm_metric") == 0 || std::strcmp(name, "sivm_init") == 0) {
+    if (c->algo != PMF_ALGO_SIVM) return fail(c, PMF_EINVAL, "sivm_metric / sivm_init: SIVM contexts only");
+    if (name[5] == 'm') {
+      if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "sivm_metric: 0 (l2), 1 (l1) or 2 (cosine)");
+      c->sv_metric = (int)value;
+      choose_stat_site(c, false);
+    } else {
+      if (value != 0 && value != 1) return fail(c, PMF_EINVAL, "sivm_init: 0 (fastmap) or 1 (origin)");
+      c->sv_init = (int)value;
+    }
     return PMF_OK;
   }
   if (std::strcmp(name, "snmf_gram") == 0) {

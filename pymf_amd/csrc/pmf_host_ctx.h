@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM };
 
 struct KernelStat {
   std::string name = "none";
@@ -161,6 +161,15 @@ struct pmf_ctx {
   bool cl_sums_valid = false;   // the slabs belong to the current V and assignment (Kmeans) / H (Cmeans).  <- V, H (Cmeans), the assignment
   bool cl_mu_valid = false;     // dClMu holds the row means of the current V.  <- V
   bool cl_err_valid = false;    // dClTot[KP] = ||V - W H||^2 of the current V, W, H (Kmeans, right behind its H step).  <- V, W, H
+  // SIVM (pmf_sivm.h): the recurrence's state ([3][np] float64), the two partials arrays of the argmax (scores, indices), select,
+  // (maxd, a); H step: the right-hand sides f + lambda [KP][np], the brackets [6][np], their sides, unfinished columns per round
+  double *dSvState = nullptr, *dSvPart = nullptr, *dSvScal = nullptr, *dSvLam = nullptr;
+  int *dSvPartIdx = nullptr, *dSvSel = nullptr, *dSvSide = nullptr, *dSvUnf = nullptr;
+  float* dSvF = nullptr;
+  int sv_wgs = 0, sv_ppw = 0;   // workgroups of k_sivm_pass, 64-column panels each owns
+  int sv_metric = 0;            // pmf_set_option("sivm_metric"): 0 l2, 1 l1, 2 cosine
+  int sv_init = 0;              // pmf_set_option("sivm_init"): 0 fastmap, 1 origin
+  bool sv_have_select = false;  // dSvSel holds the selection of a W step
   double lamb_w = 0.0, lamb_h = 0.0;   // BNMF penalty weights (bnmf.py:84-85,118-119)
   // streamed V (pmf_stream_*): row tiles pass through two device buffers, V is never resident
   float* dTile[2] = {nullptr, nullptr};

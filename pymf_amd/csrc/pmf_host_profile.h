@@ -19,6 +19,12 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.name = buf;
     st.flops = st.exec_flops = 4.0 * m * n * k;                  // W^T V and V H^T
     st.bytes = 4.0 * (m * n + k * n + 2.0 * m * k);              // V once, H written, W read, the sums written
+  } else if (c->algo == PMF_ALGO_SIVM) {
+    st.site = SITE_SIVM;
+    snprintf(buf, sizeof(buf), "k_sivm_pass<%s>", c->sv_metric == 0 ? "l2" : c->sv_metric == 1 ? "l1" : "cosine");
+    st.name = buf;
+    st.flops = st.exec_flops = 3.0 * m * n;                       // difference, square, sum
+    st.bytes = 4.0 * m * (double)c->np + 48.0 * (double)c->np;   // V once; three float64 state arrays read and written
   } else if (c->algo == PMF_ALGO_SNMF && gram) {
     st.site = SITE_MATERIALIZE;                   // the only m-sized kernel of a Gram-space loop: W = V M, once
     if (use_csr(c)) {

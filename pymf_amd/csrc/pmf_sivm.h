@@ -1,0 +1,334 @@
+// pmf_sivm.h -- SIVM (pymf/sivm.py): simplex volume maximisation, the column selection of update_w and the multiplier search
+// of the simplex-constrained H step.
+//
+// update_w (sivm.py:145-201) is num_bases + 2 ('fastmap') or num_bases ('origin') dependent passes over V [mp][np]: the
+// distance of every column to ONE selected column x = V[:, idx], a pointwise recurrence on three float64 arrays, an argmax.
+// k_sivm_pass<METRIC> is one such pass.  A workgroup owns a contiguous range of 64-column panels (a lane: 4 adjacent columns,
+// one 16-byte read per row, walking down the rows); x is gathered into LDS once per launch (idx = -1: x = 0, the 'origin'
+// initialisation, no gather).  The distance is formed from the difference, as dist.py:57-63 does, in fp32 with four
+// independent partial sums per column:  l2 sqrt(sum (v - x)^2),  l1 sum |v - x|,  cosine 1 - v.x / (|v| |x| + 1e-9).
+// Recurrence (sivm.py:181-190, float64), d = log(dist + 1e-8):
+//   d_i_times_d_j += d d_sum;  d_sum += d;  d_square += d^2;  score = d_i_times_d_j + a d_sum - (l / 2) d_square
+// with a = log(maxd).  The three fastmap passes (sivm.py:153-155) run the same kernel "plain": score = dist, state untouched.
+// Argmax without a host round trip and without float atomics: every workgroup writes (best score, lowest column attaining
+// it) into a partials array; the NEXT launch reduces the <= PMF_CL_MAX_WGS partials in its prologue -- every workgroup the
+// same way, the lowest index winning ties -- and works on that idx; workgroup 0 appends it to select[] and, behind the last
+// plain pass, writes maxd and a.  k_sivm_close does the last reduce, k_sivm_gather writes W = V[:, select] (a -1 entry is a
+// Python index there: the LAST data column).  Pad columns (c >= n) never win.  Two runs give the same bits.
+#pragma once
+#include "pmf_dev.h"
+
+enum { PMF_SIVM_L2 = 0, PMF_SIVM_L1 = 1, PMF_SIVM_COSINE = 2 };
+constexpr int PMF_SIVM_MAX_M = 16384;   // x is staged whole in LDS (m floats of dynamic shared memory: 64 KiB at the limit)
+
+struct SivmArgs {
+  const float* V;          // [mp][np]
+  double* dij;             // [np] d_i_times_d_j
+  double* dsum;            // [np] d_sum
+  double* dsq;             // [np] d_square
+  const double* pscore_in; // partials of the previous launch ...
+  const int* pidx_in;
+  double* pscore_out;      // ... and of this one, [wgs]
+  int* pidx_out;
+  int* select;             // [k]
+  double* scal;            // [0] maxd, [1] a = log(maxd)
+  int64_t np;
+  int m, n;
+  int npanels, panels_per_wg;
+  int nprev;               // partials of the previous launch to reduce in the prologue (0: none)
+  int use_fixed;           // idx = fixed_idx (the first fastmap pass: column 0; 'origin': -1) instead of the prologue's argmax
+  int fixed_idx;
+  int sel_pos;             // >= 0: workgroup 0 writes select[sel_pos] = idx
+  int take_maxd;           // the best score of the previous (plain) launch is maxd: a = log of it, workgroup 0 stores both
+  int plain;               // score = dist, state untouched
+  int l;                   // step of the recurrence (sivm.py:181)
+};
+
+// (score, index): a greater score wins, then the lower index
+__device__ __forceinline__ void sivm_better(double& s, int& i, double os, int oi) {
+  if (os > s || (os == s && oi < i)) { s = os; i = oi; }
+}
+
+// the workgroup's best of (s, i) over its 256 threads, in thread 0 (and in sb[0], ib[0])
+__device__ __forceinline__ void sivm_wg_best(double& s, int& i, double* sb, int* ib) {
+#pragma unroll
+  for (int x = 1; x < 64; x <<= 1) {
+    const double os = __shfl_xor(s, x);
+    const int oi = __shfl_xor(i, x);
+    sivm_better(s, i, os, oi);
+  }
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { sb[wave] = s; ib[wave] = i; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) sivm_better(s, i, sb[w], ib[w]);
+    sb[0] = s; ib[0] = i;
+  }
+  __syncthreads();
+}
+
+// the argmax over the previous launch's partials (every workgroup alike); n: an index outside [0, n) -- no finite score at
+// all -- becomes 0, so that nothing is ever gathered from outside V
+__device__ __forceinline__ void sivm_reduce_partials(const double* ps, const int* pi, int count, int n, double* sb, int* ib,
+                                                     double* best, int* idx) {
+  double s = -INFINITY;
+  int i = 0x7fffffff;
+  for (int q = threadIdx.x; q < count; q += 256) sivm_better(s, i, ps[q], pi[q]);
+  sivm_wg_best(s, i, sb, ib);
+  *best = sb[0];
+  *idx = ((unsigned)ib[0] < (unsigned)n) ? ib[0] : 0;
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_sivm_pass(const SivmArgs a) {
+  extern __shared__ float xs[];                 // [m]
+  __shared__ double sb[4];
+  __shared__ int ib[4];
+  const int tid = threadIdx.x;
+  const int64_t np = a.np;
+
+  // ---- prologue: which column this pass measures against ----------------------------------------------------------
+  int idx = a.fixed_idx;
+  double a_log = 0.0;
+  if (a.nprev > 0) {
+    double best;
+    int bi;
+    sivm_reduce_partials(a.pscore_in, a.pidx_in, a.nprev, a.n, sb, ib, &best, &bi);
+    if (!a.use_fixed) idx = bi;
+    if (a.take_maxd) {
+      a_log = log(best);
+      if (blockIdx.x == 0 && tid == 0) { a.scal[0] = best; a.scal[1] = a_log; }
+    }
+  }
+  if (!a.take_maxd && !a.plain) a_log = a.scal[1];
+  if (blockIdx.x == 0 && tid == 0 && a.sel_pos >= 0) a.select[a.sel_pos] = idx;
+
+  const int c_begin = blockIdx.x * a.panels_per_wg * 64;
+  const int c_end = min((blockIdx.x + 1) * a.panels_per_wg, a.npanels) * 64;
+  const int nquads = (c_end - c_begin) / 4;
+  const float* xcol = a.V + (idx >= 0 ? idx : 0);
+
+  double bs = -INFINITY;
+  int bidx = 0x7fffffff;
+  for (int r = tid; r < a.m; r += 256) xs[r] = idx >= 0 ? xcol[(int64_t)r * np] : 0.f;
+  __syncthreads();
+
+  for (int q = tid; q < nquads; q += 256) {
+    const int c = c_begin + 4 * q;
+    const float* vp = a.V + c;
+    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;        // l2 / l1: the distance sums; cosine: v . x
+    f32x4 n0 = s0, n1 = s0, n2 = s0, n3 = s0;                          // cosine: |v|^2
+    float x0 = 0.f, x1 = 0.f, x2 = 0.f, x3 = 0.f;                      // cosine: |x|^2
+    auto step = [&](const f32x4 v, const float x, f32x4& s, f32x4& nn, float& xx) {
+      if (METRIC == PMF_SIVM_L2) {
+        const f32x4 d = v - x;
+        s += d * d;
+      } else if (METRIC == PMF_SIVM_L1) {
+        const f32x4 d = v - x;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[e] += fabsf(d[e]);
+      } else {
+        s += v * x;
+        nn += v * v;
+        xx = fmaf(x, x, xx);
+      }
+    };
+    int r = 0;
+    for (; r + 4 <= a.m; r += 4) {
+      const f32x4 v0 = *reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 0) * np);
+      const f32x4 v1 = *reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 1) * np);
+      const f32x4 v2 = *reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 2) * np);
+      const f32x4 v3 = *reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 3) * np);
+      step(v0, xs[r + 0], s0, n0, x0);
+      step(v1, xs[r + 1], s1, n1, x1);
+      step(v2, xs[r + 2], s2, n2, x2);
+      step(v3, xs[r + 3], s3, n3, x3);
+    }
+    if (r < a.m) step(*reinterpret_cast<const f32x4*>(vp + (int64_t)r * np), xs[r], s0, n0, x0);
+    if (r + 1 < a.m) step(*reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 1) * np), xs[r + 1], s1, n1, x1);
+    if (r + 2 < a.m) step(*reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 2) * np), xs[r + 2], s2, n2, x2);
+    const f32x4 st = (s0 + s1) + (s2 + s3);
+    f32x4 dist;
+    if (METRIC == PMF_SIVM_L2) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dist[e] = sqrtf(st[e]);
+    } else if (METRIC == PMF_SIVM_L1) {
+      dist = st;
+    } else {
+      const f32x4 nt = (n0 + n1) + (n2 + n3);
+      const float xn = sqrtf((x0 + x1) + (x2 + x3));
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dist[e] = 1.f - st[e] / (sqrtf(nt[e]) * xn + 1e-9f);
+    }
+    if (a.plain) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (c + e < a.n) sivm_better(bs, bidx, (double)dist[e], c + e);
+    } else {
+      const double hl = 0.5 * (double)a.l;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (c + e >= a.n) continue;
+        const double d = log((double)dist[e] + 1e-8);
+        const double ds_old = a.dsum[c + e];
+        const double dij = a.dij[c + e] + d * ds_old;
+        const double ds = ds_old + d;
+        const double dq = a.dsq[c + e] + d * d;
+        a.dij[c + e] = dij;
+        a.dsum[c + e] = ds;
+        a.dsq[c + e] = dq;
+        sivm_better(bs, bidx, dij + a_log * ds - hl * dq, c + e);
+      }
+    }
+  }
+  sivm_wg_best(bs, bidx, sb, ib);
+  if (tid == 0) { a.pscore_out[blockIdx.x] = bs; a.pidx_out[blockIdx.x] = bidx; }
+}
+
+// the reduce behind the last pass: select[sel_pos] (and maxd, a when no recurrence pass followed the plain ones: num_bases = 1)
+__global__ __launch_bounds__(256) void k_sivm_close(const double* __restrict__ ps, const int* __restrict__ pi, int count, int n, int sel_pos,
+                                                    int take_maxd, int origin_first, int* __restrict__ select, double* __restrict__ scal) {
+  __shared__ double sb[4];
+  __shared__ int ib[4];
+  double best;
+  int idx;
+  sivm_reduce_partials(ps, pi, count, n, sb, ib, &best, &idx);
+  if (threadIdx.x == 0) {
+    select[sel_pos] = origin_first ? -1 : idx;
+    if (take_maxd) { scal[0] = best; scal[1] = log(best); }
+  }
+}
+
+// W [mp][KP] = V[:, select] in selection order; -1 is the last data column (a Python index, sivm.py:198); padding zero
+__global__ __launch_bounds__(256) void k_sivm_gather(const float* __restrict__ V, int64_t np, int m, int n, int k, int KP, int64_t elems,
+                                                     const int* __restrict__ select, float* __restrict__ W) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= elems) return;
+  const int64_t r = i / KP;
+  const int j = (int)(i % KP);
+  float w = 0.f;
+  if (r < m && j < k) {
+    int s = select[j];
+    if (s < 0) s += n;
+    s = min(max(s, 0), n - 1);
+    w = V[r * np + s];
+  }
+  W[i] = w;
+}
+
+// ---- the H step (aa.py:93-111): min 1/2 x^T (W^T W) x - (W^T v)^T x, x >= 0, sum x = 1, one problem per column ---------------
+// For a fixed multiplier lambda this is the non-negative QP with right-hand side f + lambda 1 (solve_nnqps); sum x(lambda) is
+// continuous, non-decreasing and piecewise linear, so a bracketing secant (Illinois) on sum x(lambda) - 1 ends after finitely
+// many rounds: lambda = -max_j f_j gives x = 0, the upper end is grown until sum x >= 1.
+
+// S = W^T W in float64 from the float32 W, [KP][KP], the identity on the padding (what the QP kernels expect)
+__global__ __launch_bounds__(256) void k_sivm_hessian(const float* __restrict__ W, int m, int k, int KP, double* __restrict__ Gd) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= KP * KP) return;
+  const int i = e / KP, j = e % KP;
+  double s = 0.0;
+  if (i < k && j < k) {
+    for (int r = 0; r < m; ++r) s = fma((double)W[(int64_t)r * KP + i], (double)W[(int64_t)r * KP + j], s);
+  } else {
+    s = i == j ? 1.0 : 0.0;
+  }
+  Gd[e] = s;
+}
+
+struct SivmLamArgs {
+  const float* PS;         // [KP][ldp]: row j, column c = (W^T v_c)_j
+  int64_t ldp;
+  float* F;                // [KP][np]: f + lambda
+  const float* X;          // [KP][np]
+  const double* Gd;        // [KP][KP] W^T W
+  const double* Binv;      // [KP][KP] its inverse
+  double* st;              // [6][np]: lam_min, lo, g_lo, hi, g_hi, lam
+  int* side;               // [np]: 0 no upper end yet; otherwise -1 / +1 = the end the last round replaced (lower / upper)
+  int* unfinished;         // [rounds + 1]
+  int64_t np;
+  int n, k, KP, round;
+  double tol;
+};
+
+// round 0: the bracket's lower end and the first multiplier -- the one of the equality-constrained problem without the
+// signs, lambda = (1 - 1^T inv(S) f) / (1^T inv(S) 1) (exact for a column inside the simplex); where that is not above the
+// lower end, lambda_min + S_jj at j = argmax f (x = e_j: sum x = 1 if no other variable enters)
+__global__ __launch_bounds__(256) void k_sivm_lam_init(const SivmLamArgs a) {
+  __shared__ double u[64];
+  __shared__ double usum;
+  if (threadIdx.x < 64) {
+    double s = 0.0;
+    if ((int)threadIdx.x < a.k)
+      for (int j = 0; j < a.k; ++j) s += a.Binv[(int64_t)threadIdx.x * a.KP + j];
+    u[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int j = 0; j < a.k; ++j) s += u[j];
+    usum = s;
+  }
+  __syncthreads();
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= a.np) return;
+  if (c >= a.n) {
+    for (int j = 0; j < a.KP; ++j) a.F[(int64_t)j * a.np + c] = 0.f;
+    return;
+  }
+  double fmax = -INFINITY, uf = 0.0;
+  int jmax = 0;
+  for (int j = 0; j < a.k; ++j) {
+    const double f = (double)a.PS[(int64_t)j * a.ldp + c];
+    if (f > fmax) { fmax = f; jmax = j; }
+    uf = fma(u[j], f, uf);
+  }
+  const double lam_min = -fmax;
+  double lam = (1.0 - uf) / usum;
+  if (!(usum > 0.0) || !(lam > lam_min)) lam = lam_min + a.Gd[(int64_t)jmax * a.KP + jmax];
+  a.st[0 * a.np + c] = lam_min;
+  a.st[1 * a.np + c] = lam_min;
+  a.st[2 * a.np + c] = -1.0;
+  a.st[3 * a.np + c] = lam_min;
+  a.st[4 * a.np + c] = 0.0;
+  a.st[5 * a.np + c] = lam;
+  a.side[c] = 0;
+  for (int j = 0; j < a.KP; ++j)
+    a.F[(int64_t)j * a.np + c] = j < a.k ? (float)((double)a.PS[(int64_t)j * a.ldp + c] + lam) : 0.f;
+}
+
+// behind a round's solve: g = sum x - 1; a column within tol is finished (its multiplier and right-hand side stay); the
+// others move their bracket and multiplier, write the new right-hand side and count themselves in unfinished[round]
+__global__ __launch_bounds__(256) void k_sivm_lam_update(const SivmLamArgs a) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= a.n) return;
+  double s = 0.0;
+  for (int j = 0; j < a.k; ++j) s += (double)a.X[(int64_t)j * a.np + c];
+  const double g = s - 1.0;
+  if (fabs(g) <= a.tol) return;
+  atomicAdd(a.unfinished + a.round, 1);
+  const double lam_min = a.st[0 * a.np + c];
+  double lo = a.st[1 * a.np + c], glo = a.st[2 * a.np + c], hi = a.st[3 * a.np + c], ghi = a.st[4 * a.np + c];
+  double lam = a.st[5 * a.np + c];
+  int side = a.side[c];
+  if (g < 0.0) {
+    lo = lam; glo = g;
+    if (side < 0) ghi *= 0.5;             // the lower end moved twice running: Illinois halves the other end's value
+    if (side != 0) side = -1;
+  } else {
+    hi = lam; ghi = g;
+    if (side > 0) glo *= 0.5;
+    side = 1;
+  }
+  if (side == 0) {
+    lam = lam + 2.0 * (lam - lam_min);    // no upper end yet: grow
+  } else {
+    double nl = (lo * ghi - hi * glo) / (ghi - glo);
+    if (!(nl > lo && nl < hi)) nl = 0.5 * (lo + hi);
+    lam = nl;
+  }
+  a.st[1 * a.np + c] = lo; a.st[2 * a.np + c] = glo; a.st[3 * a.np + c] = hi; a.st[4 * a.np + c] = ghi;
+  a.st[5 * a.np + c] = lam;
+  a.side[c] = side;
+  for (int j = 0; j < a.k; ++j) a.F[(int64_t)j * a.np + c] = (float)((double)a.PS[(int64_t)j * a.ldp + c] + lam);
+}
