@@ -60,11 +60,11 @@ enum {
   PMF_ENCCL = -3,    /* an RCCL call failed */
   PMF_ENOMEM = -4,   /* device or host allocation failed */
   PMF_ESINGULAR = -5, /* SNMF: H H^T is singular (the reference's np.linalg.inv raises LinAlgError, snmf.py:69) */
-  PMF_ENUMERIC = -6   /* an iteration with a fixed cap of rounds did not finish (SIVM: the multiplier search of the H step) */
+  PMF_ENUMERIC = -6   /* an iteration with a fixed cap of rounds did not finish (SIVM, AA: the multiplier search of the H step; AA: the rounds of the W step) */
 };
 
 enum { PMF_ALGO_NMF = 0, PMF_ALGO_NMFALS = 1, PMF_ALGO_SNMF = 2, PMF_ALGO_BNMF = 3, PMF_ALGO_RNMF = 4, PMF_ALGO_CNMF = 5,
-       PMF_ALGO_KMEANS = 6, PMF_ALGO_CMEANS = 8, PMF_ALGO_SIVM = 10 };   /* 7 and 9 are not assigned: pmf_ctx_create refuses them */
+       PMF_ALGO_KMEANS = 6, PMF_ALGO_CMEANS = 8, PMF_ALGO_SIVM = 10, PMF_ALGO_AA = 11 };   /* 7 and 9 are not assigned: pmf_ctx_create refuses them */
 
 /* pmf_factorize flags (the reference's factorize() keyword arguments, nmf.py:141-142) */
 enum { PMF_COMPUTE_W = 1u, PMF_COMPUTE_H = 2u, PMF_COMPUTE_ERR = 4u };
@@ -233,6 +233,20 @@ int pmf_cluster_set_assigned(pmf_ctx* ctx, const int32_t* assigned);
  * pmf_sivm_get_select: the num_bases selected column indices of the last pmf_update_w in selection order; under 'origin' the
  * first is -1, which W treats as a Python index (the LAST data column, sivm.py:198). */
 int pmf_sivm_get_select(pmf_ctx* ctx, int32_t* select);
+
+/* AA (algo 11; pymf/aa.py, archetypal analysis: column i of W is the projection of (data pinv(H))[:, i] onto the convex hull of
+ * the data columns, W = data beta^T with beta >= 0 and rows summing to 1; the H step is the one SIVM inherits).  Dense resident
+ * data, one rank, num_bases <= 64, min(data_dimension + 1, num_samples) <= 128 (a base's corral of data columns).
+ *   pmf_update_w     AA.update_w (aa.py:113-134) as column generation (pmf_aa.h): W_hat through inv(H H^T) -- an H without full
+ *                    row rank is PMF_EINVAL --, then rounds of one pricing pass over V and one master step per base; a first
+ *                    batch of rounds is enqueued blind, then one counter is read per round; PMF_ENUMERIC when the cap of
+ *                    rounds is reached.  Needs V and H.  Two runs give the same bits.
+ *   pmf_update_h     AA.update_h (aa.py:93-111), as for SIVM.          pmf_frobenius: the direct residual.
+ *   pmf_factorize    NMF.factorize's loop (W step, H step, error, convergence test) for any niter.
+ * pmf_aa_get_beta: beta of the last pmf_update_w, num_bases x num_samples float64, row-major.
+ * pmf_aa_rounds: the rounds that W step took. */
+int pmf_aa_get_beta(pmf_ctx* ctx, double* beta);
+int pmf_aa_rounds(pmf_ctx* ctx, int32_t* rounds);
 
 /* Device time (ms, HIP events on the library's stream) of the last pmf_factorize loop. */
 int pmf_last_loop_ms(pmf_ctx* ctx, double* ms);

@@ -13,7 +13,8 @@ from .cnmf import CNMF        # noqa: F401  (convex NMF)
 from .kmeans import Kmeans    # noqa: F401  
 from .cmeans import Cmeans    # noqa: F401  
 from .sivm import SIVM        # noqa: F401  
+from .aa import AA            # noqa: F401  
 from . import dist            # noqa: F401
 
-__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "dist"]
+__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "dist"]
 __version__ = "0.1.0"

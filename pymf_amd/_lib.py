@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PMF_LIB") or os.path.join(_HERE, "csrc", "libpymf_hip.so")   # PMF_LIB: A/B builds
 
 PMF_OK, PMF_EINVAL, PMF_EHIP, PMF_ENCCL, PMF_ENOMEM, PMF_ESINGULAR, PMF_ENUMERIC = 0, -1, -2, -3, -4, -5, -6
-ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF, ALGO_KMEANS, ALGO_CMEANS, ALGO_SIVM = 0, 1, 2, 3, 4, 5, 6, 8, 10   # (7, 9: not assigned)
+ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF, ALGO_KMEANS, ALGO_CMEANS, ALGO_SIVM, ALGO_AA = 0, 1, 2, 3, 4, 5, 6, 8, 10, 11   # (7, 9: not assigned)
 COMPUTE_W, COMPUTE_H, COMPUTE_ERR = 1, 2, 4
 STREAM_RESID = 8
 NCCL_ID_BYTES = 128
@@ -66,6 +66,8 @@ SYMBOLS = [
     ("pmf_cluster_get_assigned", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_cluster_set_assigned", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_sivm_get_select", _c.c_int, [_ctx, _c.c_void_p]),
+    ("pmf_aa_get_beta", _c.c_int, [_ctx, _c.c_void_p]),
+    ("pmf_aa_rounds", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_stream_begin", _c.c_int, [_ctx, _c.c_uint32, _c.c_int64]),
     ("pmf_stream_tile", _c.c_int, [_ctx, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64]),
     ("pmf_stream_end", _c.c_int, [_ctx, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int32)]),
@@ -377,6 +379,18 @@ class Context(object):
         out = np.empty(self.k, dtype=np.int32)
         self._chk(self._lib.pmf_sivm_get_select(self._h, out.ctypes.data))
         return out
+
+    def get_beta(self):
+        """AA: beta of the last update_w, num_bases x num_samples float64 (pmf_aa_get_beta)."""
+        out = np.empty((self.k, self.n), dtype=np.float64)
+        self._chk(self._lib.pmf_aa_get_beta(self._h, out.ctypes.data))
+        return out
+
+    def aa_rounds(self):
+        """AA: rounds of pricing pass and master step the last update_w took (pmf_aa_rounds)."""
+        r = ctypes.c_int32(0)
+        self._chk(self._lib.pmf_aa_rounds(self._h, ctypes.byref(r)))
+        return int(r.value)
 
     def get_h64(self):
         H = np.empty((self.k, self.n), dtype=np.float64)

@@ -37,6 +37,7 @@
 #include "pmf_cnmf.h"
 #include "pmf_cluster.h"
 #include "pmf_sivm.h"
+#include "pmf_aa.h"
 
 // the internal host code, by concern (each header: one anonymous-namespace block; the order is the dependency order)
 #include "pmf_host_ctx.h"
@@ -52,6 +53,7 @@
 #include "pmf_host_cnmf.h"
 #include "pmf_host_cluster.h"
 #include "pmf_host_sivm.h"
+#include "pmf_host_aa.h"
 #include "pmf_host_factorize.h"
 
 // =============================================================================================
@@ -78,8 +80,8 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                    int32_t rank, int32_t nranks, const void* nccl_id) {
   if (!out) return fail(nullptr, PMF_EINVAL, "out is NULL");
   *out = nullptr;
-  if (algo < 0 || algo > 10 || algo == 7 || algo == 9)
-    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans), 8 (Cmeans) or 10 (SIVM)");
+  if (algo < 0 || algo > 11 || algo == 7 || algo == 9)
+    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans), 8 (Cmeans), 10 (SIVM) or 11 (AA)");
   if (m_local < 1 || n < 1 || k < 1) return fail(nullptr, PMF_EINVAL, "m, n, k must be >= 1");
   if (algo == PMF_ALGO_CNMF) {  // C = V^T V is n x n float64 (128 MiB at the limit); the k x k factors on one float64 MFMA tile row
     if (n > 4096) return fail(nullptr, PMF_EINVAL, "CNMF: n (samples) > 4096 is not supported by this build");
@@ -96,6 +98,12 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
     if (k > 64) return fail(nullptr, PMF_EINVAL, "SIVM: num_bases > 64 is not supported by this build");
     if (m_local > PMF_SIVM_MAX_M) return fail(nullptr, PMF_EINVAL, "SIVM: data_dimension > 16384 is not supported by this build");
     if (nranks > 1) return fail(nullptr, PMF_EINVAL, "SIVM: one rank only in this build");
+  }
+  if (algo == PMF_ALGO_AA) {    // the H step is SIVM's; a base's corral holds an affinely independent set of data columns: at most min(m + 1, n)
+    if (k > 64) return fail(nullptr, PMF_EINVAL, "AA: num_bases > 64 is not supported by this build");
+    if (std::min<int64_t>(m_local + 1, n) > PMF_AA_MAX_CORRAL)
+      return fail(nullptr, PMF_EINVAL, "AA: min(data_dimension + 1, num_samples) > 128 (the corral bound) is not supported by this build");
+    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "AA: one rank only in this build");
   }
   // The reference has no limit on num_bases (nmf.py:116-120); the generic kernels beyond 128 bases have been checked against
   // the float64 oracles at 1 500, 2 304 and 2 432 bases (tests/sweeps/bigk_limit_probe.py, tests/test_gpu_bigk.py); beyond 2 432 (19 blocks of 128)
@@ -214,6 +222,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
   if (algo == PMF_ALGO_CNMF) c->path = "cnmf_gram";
   if (cluster) c->path = "cluster_panels";
   if (algo == PMF_ALGO_SIVM) c->path = "sivm_panels";
+  if (algo == PMF_ALGO_AA) c->path = "aa_pricing";
   choose_stat_site(c, false);
   *out = c;
   return PMF_OK;
@@ -448,6 +457,13 @@ int pmf_update_w(pmf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
   }
+  if (c && c->algo == PMF_ALGO_AA) {                   // (W_hat = data pinv(H): the W step reads the data and H, aa.py:113-134)
+    PMFCHK(need(c, true, false, true));
+    if (c->v_csr) return fail(c, PMF_EINVAL, "AA: dense data only");
+    PMFCHK(aa_update_w(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMF_OK;
+  }
   PMFCHK(need(c, true, true, true));
   PMFCHK(do_update_w(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -468,6 +484,14 @@ int pmf_update_h(pmf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
   }
+  if (c && c->algo == PMF_ALGO_AA) {                   // aa.py:93-111, the step SIVM inherits
+    PMFCHK(need(c, true, true, false));
+    if (c->v_csr) return fail(c, PMF_EINVAL, "AA: dense data only");
+    c->g_valid = false;                                // (the step forms W^T W where H H^T was)
+    PMFCHK(sivm_update_h(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMF_OK;
+  }
   PMFCHK(need(c, true, true, true));
   PMFCHK(do_update_h(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -480,7 +504,7 @@ int pmf_frobenius(pmf_ctx* c, double* out) {
     PMFCHK(cnmf_ready(c));
     return cnmf_error(c, false, out);
   }
-  if (is_cluster(c) || c->algo == PMF_ALGO_SIVM) return frobenius_direct(c, out);
+  if (is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA) return frobenius_direct(c, out);
   PMFCHK(do_frobenius(c, out));
   return ipc_check(c);
 }
@@ -489,11 +513,17 @@ int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, do
                   int32_t* iters_done, int32_t* converged_at) {
   const bool cw = flags & PMF_COMPUTE_W, ch = flags & PMF_COMPUTE_H, ce = flags & PMF_COMPUTE_ERR;
   if (c && c->algo == PMF_ALGO_SIVM) PMFCHK(need(c, true, !cw, !ch));   // (either step writes its factor from scratch)
+  else if (c && c->algo == PMF_ALGO_AA) PMFCHK(need(c, true, !cw, cw || !ch));   // (the W step reads H, the H step W)
   else PMFCHK(need(c, true, true, true));
   if (niter < 0 || (ce && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
   if (iters_done) *iters_done = 0;
   if (converged_at) *converged_at = -1;
   if (c->algo == PMF_ALGO_SIVM) { SivmLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
+  if (c->algo == PMF_ALGO_AA) {
+    if (c->v_csr) return fail(c, PMF_EINVAL, "AA: dense data only");
+    AaLoopSteps s{cw, ch};
+    return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at);
+  }
   if (is_cluster(c)) { ClusterLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
   if (c->algo == PMF_ALGO_CNMF) {
     PMFCHK(cnmf_ready(c));
@@ -525,6 +555,23 @@ int pmf_sivm_get_select(pmf_ctx* c, int32_t* select) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(select, c->dSvSel, (size_t)c->k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PMF_OK;
+}
+
+int pmf_aa_get_beta(pmf_ctx* c, double* beta) {
+  if (!c || !beta) return fail(c, PMF_EINVAL, "pmf_aa_get_beta: bad arguments");
+  if (c->algo != PMF_ALGO_AA) return fail(c, PMF_EINVAL, "pmf_aa_get_beta: AA only");
+  if (!c->aa_have_beta) return fail(c, PMF_EINVAL, "pmf_aa_get_beta: no beta yet (update_w has not run)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(beta, c->dAaBeta, (size_t)c->k * c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PMF_OK;
+}
+
+int pmf_aa_rounds(pmf_ctx* c, int32_t* rounds) {
+  if (!c || !rounds) return fail(c, PMF_EINVAL, "pmf_aa_rounds: bad arguments");
+  if (c->algo != PMF_ALGO_AA) return fail(c, PMF_EINVAL, "pmf_aa_rounds: AA only");
+  *rounds = c->aa_rounds;
   return PMF_OK;
 }
 
@@ -601,7 +648,7 @@ int pmf_rnmf_set_s_f32(pmf_ctx* c, const float* S) {
 int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (c) c->hd_synced = false;
   if (!c) return PMF_EINVAL;
-  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c) || c->algo == PMF_ALGO_SIVM)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
+  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (!c->have_w || !c->have_h) return fail(c, PMF_EINVAL, "pmf_stream_begin: W and H must be set");
   if (max_tile_rows < 1) return fail(c, PMF_EINVAL, "pmf_stream_begin: max_tile_rows must be >= 1");

@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_AA };
 
 struct KernelStat {
   std::string name = "none";
@@ -170,6 +170,14 @@ struct pmf_ctx {
   int sv_metric = 0;            // pmf_set_option("sivm_metric"): 0 l2, 1 l1, 2 cosine
   int sv_init = 0;              // pmf_set_option("sivm_init"): 0 fastmap, 1 origin
   bool sv_have_select = false;  // dSvSel holds the selection of a W step
+  // AA (pmf_aa.h): W_hat, the points X and residuals R ([mp][KP]); the two partials arrays of the pricing pass ([2][wgs][KP]); per
+  // base the corral's Gram matrix, data columns and weights by slot, the finished flag; unfinished bases per round; the
+  // inverse's verdict (zero pivot, pivots above 1e-8), inv(H H^T), beta [k][n]
+  float *dAaWhat = nullptr, *dAaX = nullptr, *dAaR = nullptr, *dAaScore = nullptr;
+  int *dAaIdx = nullptr, *dAaSlot = nullptr, *dAaFin = nullptr, *dAaUnf = nullptr, *dAaFlag = nullptr;
+  double *dAaGram = nullptr, *dAaLam = nullptr, *dAaGinv = nullptr, *dAaBeta = nullptr;
+  int aa_rounds = 0;            // rounds the last W step took
+  bool aa_have_beta = false;    // dAaBeta holds the weights of a W step
   double lamb_w = 0.0, lamb_h = 0.0;   // BNMF penalty weights (bnmf.py:84-85,118-119)
   // streamed V (pmf_stream_*): row tiles pass through two device buffers, V is never resident
   float* dTile[2] = {nullptr, nullptr};

@@ -25,6 +25,12 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.name = buf;
     st.flops = st.exec_flops = 3.0 * m * n;                       // difference, square, sum
     st.bytes = 4.0 * m * (double)c->np + 48.0 * (double)c->np;   // V once; three float64 state arrays read and written
+  } else if (c->algo == PMF_ALGO_AA) {
+    st.site = SITE_AA;
+    snprintf(buf, sizeof(buf), "k_aa_price<%d>", c->NT);
+    st.name = buf;
+    st.flops = st.exec_flops = 2.0 * m * n * k;                   // G = R^T V
+    st.bytes = 4.0 * m * (double)c->np;                          // V once
   } else if (c->algo == PMF_ALGO_SNMF && gram) {
     st.site = SITE_MATERIALIZE;                   // the only m-sized kernel of a Gram-space loop: W = V M, once
     if (use_csr(c)) {

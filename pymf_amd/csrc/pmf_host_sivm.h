@@ -11,12 +11,18 @@ constexpr int PMF_SIVM_ROUND_CAP = 48;
 constexpr int PMF_SIVM_BLIND_ROUNDS = 8;
 constexpr double PMF_SIVM_SUM_TOL = 1e-6;   // |sum x - 1|: eight units in the last place of a float32 one
 
-int sivm_alloc(pmf_ctx* c) {
-  if (c->dSvState) return PMF_OK;
-  const int npanels = c->np / 64;               // (the partition of cluster_alloc, without its slab limit)
+// contiguous ranges of 64-column panels over at most PMF_CL_MAX_WGS workgroups (the partition of cluster_alloc, without its
+// slab limit): k_sivm_pass and k_aa_price
+void panel_partition(pmf_ctx* c) {
+  const int npanels = c->np / 64;
   const int want = std::min(npanels, PMF_CL_MAX_WGS);
   c->sv_ppw = (npanels + want - 1) / want;
   c->sv_wgs = (npanels + c->sv_ppw - 1) / c->sv_ppw;
+}
+
+int sivm_alloc(pmf_ctx* c) {
+  if (c->dSvState) return PMF_OK;
+  panel_partition(c);
   PMFCHK(dalloc(c, &c->dSvState, (size_t)3 * c->np));
   PMFCHK(dalloc(c, &c->dSvPart, (size_t)2 * PMF_CL_MAX_WGS));
   PMFCHK(dalloc(c, &c->dSvPartIdx, (size_t)2 * PMF_CL_MAX_WGS));
