@@ -38,6 +38,7 @@
  *   pmf_set/get_g_f64     self.G of CNMF               pymf/cnmf.py:95-100
  *   pmf_cluster_get/set_assigned  self.assigned of Kmeans  pymf/kmeans.py:77 (algo 6)
  *   pmf_sivm_get_select   self.select of SIVM          pymf/sivm.py:145-166,193 (algo 10)
+ *   pmf_svd_decompose / pmf_svd_get  SVD.factorize, U / S / V  pymf/svd.py:110-158 (algo 12; PCA: pymf/pca.py)
  *
  * Every function returns PMF_OK (0) or a negative status and never throws;
  * pmf_last_error() gives a human-readable message for the last failure.
@@ -64,7 +65,7 @@ enum {
 };
 
 enum { PMF_ALGO_NMF = 0, PMF_ALGO_NMFALS = 1, PMF_ALGO_SNMF = 2, PMF_ALGO_BNMF = 3, PMF_ALGO_RNMF = 4, PMF_ALGO_CNMF = 5,
-       PMF_ALGO_KMEANS = 6, PMF_ALGO_CMEANS = 8, PMF_ALGO_SIVM = 10, PMF_ALGO_AA = 11 };   /* 7 and 9 are not assigned: pmf_ctx_create refuses them */
+       PMF_ALGO_KMEANS = 6, PMF_ALGO_CMEANS = 8, PMF_ALGO_SIVM = 10, PMF_ALGO_AA = 11, PMF_ALGO_PCA = 12 };   /* 7 and 9 are not assigned: pmf_ctx_create refuses them */
 
 /* pmf_factorize flags (the reference's factorize() keyword arguments, nmf.py:141-142) */
 enum { PMF_COMPUTE_W = 1u, PMF_COMPUTE_H = 2u, PMF_COMPUTE_ERR = 4u };
@@ -247,6 +248,27 @@ int pmf_sivm_get_select(pmf_ctx* ctx, int32_t* select);
  * pmf_aa_rounds: the rounds that W step took. */
 int pmf_aa_get_beta(pmf_ctx* ctx, double* beta);
 int pmf_aa_rounds(pmf_ctx* ctx, int32_t* rounds);
+
+/* PCA / SVD (algo 12; pymf/svd.py:110-158 for dense data, pymf/pca.py): the SVD of the resident V through the eigen-decomposition
+ * of its Gram matrix on the short side -- V^T V for rows > cols (_left_svd), V V^T otherwise (_right_svd) -- formed in float64
+ * on the float64 MFMA (k_gram_f64), decomposed by the float64 Jacobi solver of pmf_nndsvd_init.  Eigenvalues <= 1e-8 are dropped
+ * as in svd.py, the rest sorted descending; the side that comes from the eigenvectors is float64, the projected side
+ * (U = data V^T S^-1 or V = S^-1 U^T data) is multiplied in float32.  Dense resident data, one rank, min(rows, cols) <= 2432,
+ * and the context's k >= min(rows, cols) (the largest possible rank; W and H are k wide) -- pmf_ctx_create returns PMF_EINVAL
+ * otherwise.  pmf_set_option "pca_num_bases" (0 = all, the default) carries PCA's num_bases.  With algo 12:
+ *   pmf_update_w     PCA.update_w (pca.py:93-108): the decomposition, then W = the leading pca_num_bases columns of U (the other
+ *                    columns zero); needs V only.  Two runs give the same bits.
+ *   pmf_update_h     PCA.update_h (pca.py:90-91): H = W^T V; needs V, W
+ *   pmf_factorize    update_w, update_h, ||V - W H|| under the PMF_COMPUTE_* flags; the class always passes niter = 1
+ *   pmf_frobenius    the direct residual
+ * pmf_svd_decompose: the decomposition alone; *rank = the number of singular triples kept.  It leaves W = U and H = S V, so
+ * that pmf_frobenius is svd.py's ||data - U S V||.
+ * pmf_svd_get: U (rows x rank), S (rank values) and V (rank x cols) of the last decomposition as float64, row-major; a NULL
+ * pointer skips that factor.  pmf_svd_rank: the rank of that decomposition (what a PCA W step found).  Both return PMF_EINVAL
+ * when the resident V has not been decomposed. */
+int pmf_svd_decompose(pmf_ctx* ctx, int32_t* rank);
+int pmf_svd_rank(pmf_ctx* ctx, int32_t* rank);
+int pmf_svd_get(pmf_ctx* ctx, double* U, double* S, double* V);
 
 /* Device time (ms, HIP events on the library's stream) of the last pmf_factorize loop. */
 int pmf_last_loop_ms(pmf_ctx* ctx, double* ms);

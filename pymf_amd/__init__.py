@@ -14,7 +14,9 @@ from .kmeans import Kmeans    # noqa: F401  
 from .cmeans import Cmeans    # noqa: F401  
 from .sivm import SIVM        # noqa: F401  
 from .aa import AA            # noqa: F401  
+from .svd import SVD          # noqa: F401  
+from .pca import PCA          # noqa: F401  
 from . import dist            # noqa: F401
 
-__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "dist"]
+__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "SVD", "PCA", "dist"]
 __version__ = "0.1.0"

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PMF_LIB") or os.path.join(_HERE, "csrc", "libpymf_hip.so")   # PMF_LIB: A/B builds
 
 PMF_OK, PMF_EINVAL, PMF_EHIP, PMF_ENCCL, PMF_ENOMEM, PMF_ESINGULAR, PMF_ENUMERIC = 0, -1, -2, -3, -4, -5, -6
-ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF, ALGO_KMEANS, ALGO_CMEANS, ALGO_SIVM, ALGO_AA = 0, 1, 2, 3, 4, 5, 6, 8, 10, 11   # (7, 9: not assigned)
+ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF, ALGO_KMEANS, ALGO_CMEANS, ALGO_SIVM, ALGO_AA, ALGO_PCA = 0, 1, 2, 3, 4, 5, 6, 8, 10, 11, 12   # (7, 9: not assigned)
 COMPUTE_W, COMPUTE_H, COMPUTE_ERR = 1, 2, 4
 STREAM_RESID = 8
 NCCL_ID_BYTES = 128
@@ -68,6 +68,9 @@ SYMBOLS = [
     ("pmf_sivm_get_select", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_aa_get_beta", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_aa_rounds", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
+    ("pmf_svd_decompose", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
+    ("pmf_svd_rank", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
+    ("pmf_svd_get", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     ("pmf_stream_begin", _c.c_int, [_ctx, _c.c_uint32, _c.c_int64]),
     ("pmf_stream_tile", _c.c_int, [_ctx, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64]),
     ("pmf_stream_end", _c.c_int, [_ctx, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int32)]),
@@ -391,6 +394,27 @@ class Context(object):
         r = ctypes.c_int32(0)
         self._chk(self._lib.pmf_aa_rounds(self._h, ctypes.byref(r)))
         return int(r.value)
+
+    def svd_decompose(self):
+        """PCA / SVD: decompose the resident V (pmf_svd_decompose); returns the number of singular triples kept."""
+        r = ctypes.c_int32(0)
+        self._chk(self._lib.pmf_svd_decompose(self._h, ctypes.byref(r)))
+        return int(r.value)
+
+    def svd_rank(self):
+        """PCA / SVD: the rank of the last decomposition of the resident V (pmf_svd_rank)."""
+        r = ctypes.c_int32(0)
+        self._chk(self._lib.pmf_svd_rank(self._h, ctypes.byref(r)))
+        return int(r.value)
+
+    def svd_get(self, rank, want="USV"):
+        """PCA / SVD: U (m x rank), the singular values (rank) and V (rank x n) of the last decomposition, float64
+        (pmf_svd_get); `rank` is what svd_decompose / svd_rank returned.  Factors not named in `want` come back as None."""
+        U = np.zeros((self.m, rank), dtype=np.float64) if "U" in want else None
+        S = np.zeros(rank, dtype=np.float64) if "S" in want else None
+        V = np.zeros((rank, self.n), dtype=np.float64) if "V" in want else None
+        self._chk(self._lib.pmf_svd_get(self._h, *(None if a is None else a.ctypes.data for a in (U, S, V))))
+        return U, S, V
 
     def get_h64(self):
         H = np.empty((self.k, self.n), dtype=np.float64)

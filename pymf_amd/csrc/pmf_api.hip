@@ -38,6 +38,7 @@
 #include "pmf_cluster.h"
 #include "pmf_sivm.h"
 #include "pmf_aa.h"
+#include "pmf_svd.h"
 
 // the internal host code, by concern (each header: one anonymous-namespace block; the order is the dependency order)
 #include "pmf_host_ctx.h"
@@ -54,6 +55,7 @@
 #include "pmf_host_cluster.h"
 #include "pmf_host_sivm.h"
 #include "pmf_host_aa.h"
+#include "pmf_host_svd.h"
 #include "pmf_host_factorize.h"
 
 // =============================================================================================
@@ -80,8 +82,8 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                    int32_t rank, int32_t nranks, const void* nccl_id) {
   if (!out) return fail(nullptr, PMF_EINVAL, "out is NULL");
   *out = nullptr;
-  if (algo < 0 || algo > 11 || algo == 7 || algo == 9)
-    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans), 8 (Cmeans), 10 (SIVM) or 11 (AA)");
+  if (algo < 0 || algo > 12 || algo == 7 || algo == 9)
+    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans), 8 (Cmeans), 10 (SIVM), 11 (AA) or 12 (PCA / SVD)");
   if (m_local < 1 || n < 1 || k < 1) return fail(nullptr, PMF_EINVAL, "m, n, k must be >= 1");
   if (algo == PMF_ALGO_CNMF) {  // C = V^T V is n x n float64 (128 MiB at the limit); the k x k factors on one float64 MFMA tile row
     if (n > 4096) return fail(nullptr, PMF_EINVAL, "CNMF: n (samples) > 4096 is not supported by this build");
@@ -104,6 +106,13 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
     if (std::min<int64_t>(m_local + 1, n) > PMF_AA_MAX_CORRAL)
       return fail(nullptr, PMF_EINVAL, "AA: min(data_dimension + 1, num_samples) > 128 (the corral bound) is not supported by this build");
     if (nranks > 1) return fail(nullptr, PMF_EINVAL, "AA: one rank only in this build");
+  }
+  if (algo == PMF_ALGO_PCA) {   // the Gram matrix on the short side goes through the full Jacobi solver; U and V travel as bases of the product paths
+    if (std::min<int64_t>(m_local, n) > PMF_SVD_MAX_RANK)
+      return fail(nullptr, PMF_EINVAL, "PCA / SVD: min(rows, cols) > 2432 is not supported by this build");
+    if (k < std::min<int64_t>(m_local, n))
+      return fail(nullptr, PMF_EINVAL, "PCA / SVD: the context's base count must be at least min(rows, cols) (the largest possible rank)");
+    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "PCA / SVD: one rank only in this build");
   }
   // The reference has no limit on num_bases (nmf.py:116-120); the generic kernels beyond 128 bases have been checked against
   // the float64 oracles at 1 500, 2 304 and 2 432 bases (tests/sweeps/bigk_limit_probe.py, tests/test_gpu_bigk.py); beyond 2 432 (19 blocks of 128)
@@ -223,6 +232,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
   if (cluster) c->path = "cluster_panels";
   if (algo == PMF_ALGO_SIVM) c->path = "sivm_panels";
   if (algo == PMF_ALGO_AA) c->path = "aa_pricing";
+  if (algo == PMF_ALGO_PCA) c->path = "svd_gram_f64";
   choose_stat_site(c, false);
   *out = c;
   return PMF_OK;
@@ -464,6 +474,12 @@ int pmf_update_w(pmf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
   }
+  if (c && c->algo == PMF_ALGO_PCA) {                  // (the decomposition reads the data alone: pca.py:93-108)
+    PMFCHK(need(c, true, false, false));
+    PMFCHK(pca_update_w(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMF_OK;
+  }
   PMFCHK(need(c, true, true, true));
   PMFCHK(do_update_w(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -492,6 +508,12 @@ int pmf_update_h(pmf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
   }
+  if (c && c->algo == PMF_ALGO_PCA) {                  // pca.py:90-91
+    PMFCHK(need(c, true, true, false));
+    PMFCHK(pca_update_h(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMF_OK;
+  }
   PMFCHK(need(c, true, true, true));
   PMFCHK(do_update_h(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -505,6 +527,7 @@ int pmf_frobenius(pmf_ctx* c, double* out) {
     return cnmf_error(c, false, out);
   }
   if (is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA) return frobenius_direct(c, out);
+  if (c->algo == PMF_ALGO_PCA) return pca_error(c, out);
   PMFCHK(do_frobenius(c, out));
   return ipc_check(c);
 }
@@ -512,13 +535,14 @@ int pmf_frobenius(pmf_ctx* c, double* out) {
 int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, double* ferr,
                   int32_t* iters_done, int32_t* converged_at) {
   const bool cw = flags & PMF_COMPUTE_W, ch = flags & PMF_COMPUTE_H, ce = flags & PMF_COMPUTE_ERR;
-  if (c && c->algo == PMF_ALGO_SIVM) PMFCHK(need(c, true, !cw, !ch));   // (either step writes its factor from scratch)
+  if (c && (c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_PCA)) PMFCHK(need(c, true, !cw, !ch));   // (either step writes its factor from scratch)
   else if (c && c->algo == PMF_ALGO_AA) PMFCHK(need(c, true, !cw, cw || !ch));   // (the W step reads H, the H step W)
   else PMFCHK(need(c, true, true, true));
   if (niter < 0 || (ce && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
   if (iters_done) *iters_done = 0;
   if (converged_at) *converged_at = -1;
   if (c->algo == PMF_ALGO_SIVM) { SivmLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
+  if (c->algo == PMF_ALGO_PCA) { PcaLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
   if (c->algo == PMF_ALGO_AA) {
     if (c->v_csr) return fail(c, PMF_EINVAL, "AA: dense data only");
     AaLoopSteps s{cw, ch};
@@ -573,6 +597,29 @@ int pmf_aa_rounds(pmf_ctx* c, int32_t* rounds) {
   if (c->algo != PMF_ALGO_AA) return fail(c, PMF_EINVAL, "pmf_aa_rounds: AA only");
   *rounds = c->aa_rounds;
   return PMF_OK;
+}
+
+int pmf_svd_decompose(pmf_ctx* c, int32_t* rank) {
+  if (c && c->algo != PMF_ALGO_PCA) return fail(c, PMF_EINVAL, "pmf_svd_decompose: PCA / SVD contexts only");
+  PMFCHK(need(c, true, false, false));
+  PMFCHK(svd_decompose(c));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (rank) *rank = c->svd_rank;
+  return PMF_OK;
+}
+
+int pmf_svd_rank(pmf_ctx* c, int32_t* rank) {
+  if (!c || !rank) return fail(c, PMF_EINVAL, "pmf_svd_rank: bad arguments");
+  if (c->algo != PMF_ALGO_PCA) return fail(c, PMF_EINVAL, "pmf_svd_rank: PCA / SVD contexts only");
+  if (!c->svd_valid) return fail(c, PMF_EINVAL, "pmf_svd_rank: no decomposition of the current data (pmf_svd_decompose / pmf_update_w first)");
+  *rank = c->svd_rank;
+  return PMF_OK;
+}
+
+int pmf_svd_get(pmf_ctx* c, double* U, double* S, double* V) {
+  if (c && c->algo != PMF_ALGO_PCA) return fail(c, PMF_EINVAL, "pmf_svd_get: PCA / SVD contexts only");
+  PMFCHK(need(c, true, false, false));
+  return svd_get(c, U, S, V);
 }
 
 int pmf_cluster_set_assigned(pmf_ctx* c, const int32_t* assigned) {
@@ -648,7 +695,7 @@ int pmf_rnmf_set_s_f32(pmf_ctx* c, const float* S) {
 int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (c) c->hd_synced = false;
   if (!c) return PMF_EINVAL;
-  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
+  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA || c->algo == PMF_ALGO_PCA)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (!c->have_w || !c->have_h) return fail(c, PMF_EINVAL, "pmf_stream_begin: W and H must be set");
   if (max_tile_rows < 1) return fail(c, PMF_EINVAL, "pmf_stream_begin: max_tile_rows must be >= 1");
@@ -1136,6 +1183,12 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
   if (std::strcmp(name, "rowgemm_stream") == 0) {
     if (value != 0 && value != 1) return fail(c, PMF_EINVAL, "rowgemm_stream: 0 or 1");
     c->opt_rowgemm_stream = (int)value;
+    return PMF_OK;
+  }
+  if (std::strcmp(name, "pca_num_bases") == 0) {
+    if (c->algo != PMF_ALGO_PCA) return fail(c, PMF_EINVAL, "pca_num_bases: PCA / SVD contexts only");
+    if (value < 0 || value > c->k) return fail(c, PMF_EINVAL, "pca_num_bases: 0 (all) .. the context's base count");
+    c->pca_bases = (int)value;
     return PMF_OK;
   }
   if (std::strcmp(name, "sivm_metric") == 0 || std::strcmp(name, "sivm_init") == 0) {

@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_AA };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_AA, SITE_SVD };
 
 struct KernelStat {
   std::string name = "none";
@@ -178,6 +178,14 @@ struct pmf_ctx {
   double *dAaGram = nullptr, *dAaLam = nullptr, *dAaGinv = nullptr, *dAaBeta = nullptr;
   int aa_rounds = 0;            // rounds the last W step took
   bool aa_have_beta = false;    // dAaBeta holds the weights of a W step
+  // SVD / PCA (pmf_svd.h): the kept eigenvectors in descending order ([KP][mp] or, rows > cols, [KP][np]; float64), the singular
+  // values [KP], the projected side in float32 (V [KP][np] or, rows > cols, U [mp][KP])
+  double *dSvdE = nullptr, *dSvdS = nullptr;
+  float* dSvdP = nullptr;
+  int svd_rank = 0;             // eigenvalues above svd.py's 1e-8 cut
+  bool svd_left = false;        // rows > cols: svd.py's _left_svd
+  bool svd_valid = false;       // dSvdE / dSvdS / dSvdP belong to the current V.  <- V
+  int pca_bases = 0;            // pmf_set_option("pca_num_bases"): columns of U that PCA's W step takes, 0 = all
   double lamb_w = 0.0, lamb_h = 0.0;   // BNMF penalty weights (bnmf.py:84-85,118-119)
   // streamed V (pmf_stream_*): row tiles pass through two device buffers, V is never resident
   float* dTile[2] = {nullptr, nullptr};
@@ -379,6 +387,7 @@ int need(pmf_ctx* c, bool v, bool w, bool h) {
 void v_replaced(pmf_ctx* c) {
   c->vnorm_valid = c->vnorm_local_valid = c->ps_valid = c->num_valid = c->trace_ready = c->c_valid = false;
   c->cl_sums_valid = c->cl_err_valid = c->cl_mu_valid = false;
+  c->svd_valid = false;
 }
 void w_replaced(pmf_ctx* c, bool by_caller) {   // by_caller: uploaded or filled through the ABI (not the NNDSVD init, not a restored snapshot)
   c->have_w = true; c->ps_valid = c->num_valid = c->trace_ready = c->w_implicit = false;

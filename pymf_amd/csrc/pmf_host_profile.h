@@ -31,6 +31,14 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.name = buf;
     st.flops = st.exec_flops = 2.0 * m * n * k;                   // G = R^T V
     st.bytes = 4.0 * m * (double)c->np;                          // V once
+  } else if (c->algo == PMF_ALGO_PCA) {
+    st.site = SITE_SVD;
+    const bool left = c->m > c->n;
+    st.name = left ? "k_gram_f64<true>" : "k_gram_f64<false>";
+    const double q = left ? n : m;
+    st.flops = 2.0 * m * n * q;                                   // the whole Gram matrix ...
+    st.exec_flops = m * n * (q + 64.0);                           // ... of which the upper block triangle is formed
+    st.bytes = 4.0 * (double)c->mp * (double)c->np;              // V once
   } else if (c->algo == PMF_ALGO_SNMF && gram) {
     st.site = SITE_MATERIALIZE;                   // the only m-sized kernel of a Gram-space loop: W = V M, once
     if (use_csr(c)) {

@@ -1,0 +1,185 @@
+// pmf_host_svd.h -- SVD / PCA: svd_dense (svd.py:110-158 for dense data) and the factors PCA takes from it (kernels: pmf_svd.h, pmf_nndsvd.h)
+// Host code of libpymf_hip.so: included by pmf_api.hip (the translation unit) in this order, nothing else includes it.
+#pragma once
+
+namespace {
+
+// chunks of the inner dimension (a multiple of 64) for `ntiles` tiles: tiles x chunks near PMF_SVD_TARGET_WGS, a chunk
+// no shorter than PMF_SVD_MIN_CHUNK and a multiple of 64 (64 x 1 048 576: one tile, 512 chunks of 2 048 columns)
+void svd_chunks(int inner, int ntiles, int* nchunks, int* chunk_len) {
+  const int nch = std::max(1, std::min(PMF_SVD_TARGET_WGS / ntiles, inner / PMF_SVD_MIN_CHUNK));
+  *chunk_len = (int)round_up((inner + nch - 1) / nch, 64);
+  *nchunks = (inner + *chunk_len - 1) / *chunk_len;
+}
+
+// A [qp][qp] float64 = V V^T (q = mp) or V^T V (trans: q = np) of the resident dense V
+int gram_f64(pmf_ctx* c, bool trans, double* A, DevTemps& tmp) {
+  const int qp = trans ? c->np : (int)c->mp, inner = trans ? (int)c->mp : c->np;
+  const int T = qp / PMF_SVD_TILE, ntiles = T * (T + 1) / 2;
+  int nch = 1, cl = inner;
+  svd_chunks(inner, ntiles, &nch, &cl);
+  double* slab = nullptr;
+  PMFCHK(talloc(c, tmp, &slab, (size_t)nch * ntiles * PMF_SVD_TILE * PMF_SVD_TILE));
+  const dim3 grid((unsigned)ntiles, (unsigned)nch);
+  stat_begin(c, SITE_SVD);
+  if (trans) hipLaunchKernelGGL(k_gram_f64<true>, grid, dim3(256), 0, c->stream, (const float*)c->dV, (int64_t)c->np, inner, cl, T, slab);
+  else hipLaunchKernelGGL(k_gram_f64<false>, grid, dim3(256), 0, c->stream, (const float*)c->dV, (int64_t)c->np, inner, cl, T, slab);
+  stat_end(c, SITE_SVD);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_gram_reduce_f64, dim3((unsigned)ntiles * 64u), dim3(1024), 0, c->stream, (const double*)slab, nch, ntiles, T, A, (int64_t)qp);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_mirror_upper_f64, dim3((unsigned)(((int64_t)qp * qp + 255) / 256)), dim3(256), 0, c->stream, A, qp);
+  HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+int svd_alloc(pmf_ctx* c) {
+  if (c->dSvdE) return PMF_OK;
+  const bool left = c->m > c->n;
+  PMFCHK(dalloc(c, &c->dSvdE, (size_t)c->KP * (left ? c->np : c->mp)));
+  PMFCHK(dalloc(c, &c->dSvdS, (size_t)c->KP));
+  PMFCHK(dalloc(c, &c->dSvdP, left ? (size_t)c->mp * c->KP : (size_t)c->KP * c->np));
+  return PMF_OK;
+}
+
+// svd.py:110-158 on the resident V.  rows > cols (_left_svd): eigenpairs of V^T V give S and the rows of V (float64, dSvdE),
+// U = data V^T S^-1 on k_rowgemm (float32, dSvdP [mp][KP]).  Otherwise (_right_svd): eigenpairs of V V^T give S and the columns
+// of U (float64, rows of dSvdE), V = S^-1 U^T data as the W^T V product of W = U S^-1 (float32, dSvdP [KP][np]); dW is left
+// holding U S^-1.  Eigenvalues <= 1e-8 are dropped (svd.py:116-117,141-142), the rest sorted descending; svd_rank = how many.
+int svd_dense(pmf_ctx* c) {
+  if (c->v_csr || !c->dV) return fail(c, PMF_EINVAL, "SVD: dense resident data only");
+  if (multi_rank(c)) return fail(c, PMF_EINVAL, "SVD: one rank only in this build");
+  if (c->svd_valid) return PMF_OK;
+  const bool left = c->m > c->n;
+  const int q = (int)(left ? c->n : c->m), qp = left ? c->np : (int)c->mp, KP = c->KP;
+  const int nj = q + (q & 1);
+  PMFCHK(svd_alloc(c));
+  DevTemps tmp;
+  double *A = nullptr, *A2 = nullptr, *QT = nullptr, *evals = nullptr;
+  float* B = nullptr;
+  int *info = nullptr, *order = nullptr;
+  PMFCHK(talloc(c, tmp, &A, (size_t)qp * qp));
+  PMFCHK(talloc(c, tmp, &A2, (size_t)qp * qp));
+  PMFCHK(talloc(c, tmp, &QT, (size_t)qp * qp));
+  PMFCHK(talloc(c, tmp, &evals, (size_t)qp));
+  PMFCHK(talloc(c, tmp, &info, 2));
+  PMFCHK(talloc(c, tmp, &order, (size_t)KP));
+  if (left) PMFCHK(talloc(c, tmp, &B, (size_t)KP * qp));
+  PMFCHK(gram_f64(c, left, A, tmp));
+  PMFCHK(jacobi_eigh_dev(c, A, A2, QT, qp, nj, evals, info));
+  std::vector<double> ev((size_t)nj);
+  HIPCHK(c, hipMemcpyAsync(ev.data(), evals, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<int> ord;
+  for (int j = 0; j < nj; ++j)
+    if (ev[(size_t)j] > 1e-8) ord.push_back(j);
+  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return ev[(size_t)a] > ev[(size_t)b]; });
+  const int r = (int)ord.size();
+  if (r > KP) return fail(c, PMF_EINVAL, "SVD: the rank exceeds the context's base count");
+  std::vector<double> sv((size_t)KP, 0.0);
+  for (int i = 0; i < r; ++i) sv[(size_t)i] = std::sqrt(ev[(size_t)ord[(size_t)i]]);
+  ord.resize((size_t)KP, 0);
+  HIPCHK(c, hipMemcpyAsync(order, ord.data(), (size_t)KP * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->dSvdS, sv.data(), (size_t)KP * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_svd_gather, dim3((unsigned)(((int64_t)KP * qp + 255) / 256)), dim3(256), 0, c->stream, (const double*)QT, qp, q, r, KP,
+                     (const int*)order, (const double*)c->dSvdS, c->dSvdE, B);
+  HIPCHK(c, hipGetLastError());
+  if (left) {
+    PMFCHK(rowgemm<EPI_STORE>(c, c->dV, c->np, c->np, B, c->np, nullptr, nullptr, c->dSvdP));
+  } else {
+    const int64_t total = c->mp * KP;
+    hipLaunchKernelGGL(k_svd_w, dim3(elem_grid(total)), dim3(256), 0, c->stream, (const double*)c->dSvdE, qp, (const float*)nullptr, 1, c->m, total, KP,
+                       r, (const double*)c->dSvdS, 1, c->dW);
+    HIPCHK(c, hipGetLastError());
+    w_replaced(c, false);
+    PMFCHK(ensure_ps(c));
+    HIPCHK(c, hipMemcpy2DAsync(c->dSvdP, (size_t)c->np * sizeof(float), c->dPS, ((size_t)c->np + KP) * sizeof(float),
+                               (size_t)c->np * sizeof(float), (size_t)KP, hipMemcpyDeviceToDevice, c->stream));
+    c->have_w = false;                                   // (U S^-1 is an operand, not a factor anybody asked for)
+    c->ps_valid = false;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
+  c->svd_rank = r; c->svd_left = left; c->svd_valid = true;
+  return PMF_OK;
+}
+
+// dW <- the leading kb columns of U (float32)
+int svd_load_w(pmf_ctx* c, int kb) {
+  const int64_t total = c->mp * c->KP;
+  hipLaunchKernelGGL(k_svd_w, dim3(elem_grid(total)), dim3(256), 0, c->stream, (const double*)c->dSvdE, (int)c->mp, (const float*)c->dSvdP,
+                     c->svd_left ? 0 : 1, c->m, total, c->KP, kb, (const double*)c->dSvdS, 0, c->dW);
+  HIPCHK(c, hipGetLastError());
+  w_replaced(c, false);
+  return PMF_OK;
+}
+
+// pmf_svd_decompose: svd_dense, then W = U and H = S V, so that pmf_frobenius is ||data - U S V|| (svd.py:92-107)
+int svd_decompose(pmf_ctx* c) {
+  PMFCHK(svd_dense(c));
+  PMFCHK(svd_load_w(c, c->svd_rank));
+  const int64_t total = (int64_t)c->KP * c->np;
+  hipLaunchKernelGGL(k_svd_h, dim3(elem_grid(total)), dim3(256), 0, c->stream, c->svd_left ? (const double*)c->dSvdE : (const double*)nullptr,
+                     (const float*)c->dSvdP, (int64_t)c->np, c->np, (int)c->n, c->svd_rank, total, (const double*)c->dSvdS, c->dH);
+  HIPCHK(c, hipGetLastError());
+  h_replaced(c, false, true);
+  return PMF_OK;
+}
+
+// PCA.update_w (pca.py:93-108): W = the leading num_bases columns of U (all of them when num_bases == 0); S is descending
+// already, so pca.py's argsort is the identity
+int pca_update_w(pmf_ctx* c) {
+  PMFCHK(svd_dense(c));
+  const int kb = c->pca_bases > 0 ? std::min(c->pca_bases, c->svd_rank) : c->svd_rank;
+  return svd_load_w(c, kb);
+}
+
+// PCA.update_h (pca.py:90-91): H = W^T data
+int pca_update_h(pmf_ctx* c) {
+  PMFCHK(ensure_ps(c));
+  HIPCHK(c, hipMemcpy2DAsync(c->dH, (size_t)c->np * sizeof(float), c->dPS, ((size_t)c->np + c->KP) * sizeof(float),
+                             (size_t)c->np * sizeof(float), (size_t)c->KP, hipMemcpyDeviceToDevice, c->stream));
+  h_replaced(c, false, true);
+  return PMF_OK;
+}
+
+// ||data - W H||: the direct residual (a full-rank PCA fits exactly: the trace identity would cancel)
+int pca_error(pmf_ctx* c, double* out) {
+  if (c->nb == 1) return frobenius_direct(c, out);
+  PMFCHK(resid_bigk(c, false, c->dScal));
+  double ss = 0.0;
+  HIPCHK(c, hipMemcpyAsync(&ss, c->dScal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *out = std::sqrt(ss);
+  return PMF_OK;
+}
+
+// U (rows x r), S (r) and V (r x cols) of the last svd_dense as float64, row-major; any of them may be null
+int svd_get(pmf_ctx* c, double* U, double* S, double* V) {
+  if (!c->svd_valid) return fail(c, PMF_EINVAL, "pmf_svd_get: no decomposition of the current data (pmf_svd_decompose / pmf_update_w first)");
+  const int r = c->svd_rank, KP = c->KP;
+  const int64_t m = c->m, n = c->n;
+  const int qp = c->svd_left ? c->np : (int)c->mp;
+  if (r == 0) return PMF_OK;
+  if (S) HIPCHK(c, hipMemcpyAsync(S, c->dSvdS, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  std::vector<double> E;
+  std::vector<float> P;
+  if ((c->svd_left && V) || (!c->svd_left && U)) {
+    E.resize((size_t)r * qp);
+    HIPCHK(c, hipMemcpyAsync(E.data(), c->dSvdE, E.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  }
+  if ((c->svd_left && U) || (!c->svd_left && V)) {
+    P.resize(c->svd_left ? (size_t)m * KP : (size_t)r * c->np);
+    HIPCHK(c, hipMemcpyAsync(P.data(), c->dSvdP, P.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->svd_left) {
+    if (V) for (int i = 0; i < r; ++i) std::memcpy(V + (size_t)i * n, E.data() + (size_t)i * qp, (size_t)n * sizeof(double));
+    if (U) for (int64_t row = 0; row < m; ++row) for (int i = 0; i < r; ++i) U[(size_t)row * r + i] = (double)P[(size_t)row * KP + i];
+  } else {
+    if (U) for (int64_t row = 0; row < m; ++row) for (int i = 0; i < r; ++i) U[(size_t)row * r + i] = E[(size_t)i * qp + row];
+    if (V) for (int i = 0; i < r; ++i) for (int64_t col = 0; col < n; ++col) V[(size_t)i * n + col] = (double)P[(size_t)i * c->np + col];
+  }
+  return PMF_OK;
+}
+
+}  // namespace

@@ -1,0 +1,95 @@
+"""pymf_amd.SVD -- drop-in for pymf.SVD (reference pymf/svd.py) on MI355X, dense data.
+
+The reference takes the SVD of the data through the eigen-decomposition of the Gram matrix on the short side
+(svd.py:110-158): data^T data for rows > cols (`_left_svd`), data data^T otherwise (`_right_svd`); eigenvalues <= 1e-8 are
+dropped, the rest sorted descending, S = sqrt, and the other side is projected (U = data V^T S^-1 or V = S^-1 U^T data).
+On the device the Gram matrix of the float32 data is formed in float64 on the float64 MFMA (k_gram_f64), decomposed by the
+float64 Jacobi solver, and the projected side is multiplied in float32.  U (rows x r), S (r x r diagonal)
+and V (r x cols) come back as float64 arrays, as the reference returns them; r is the number of eigenvalues kept.
+
+Supported: dense data, one rank, min(rows, cols) <= 2432.  scipy.sparse data raises TypeError, a multi-rank world
+NotImplementedError, a larger short side ValueError.  `k` is accepted and ignored for dense data, as in svd.py.  There is
+no `pinv` yet.
+"""
+import warnings
+
+import numpy as np
+
+from . import _lib
+from . import dist as _dist
+from .nmf import PrecisionWarning, _is_sparse
+
+__all__ = ["SVD"]
+
+MAX_RANK = 2432   # PMF_SVD_MAX_RANK (pmf_svd.h)
+
+
+class SVD(object):
+    """
+    SVD(data, k=-1, rrank=0, crank=0)
+
+    >>> data = np.array([[1.0, 0.0, 2.0], [0.0, 1.0, 1.0]])
+    >>> svd_mdl = SVD(data)
+    >>> svd_mdl.factorize()
+    """
+    _EPS = 10 ** -8                                            # svd.py:74
+
+    def __init__(self, data, k=-1, rrank=0, crank=0):          # svd.py:76-90
+        self.data = data
+        (self._rows, self._cols) = self.data.shape
+        self._rrank = rrank if rrank > 0 else self._rows
+        self._crank = crank if crank > 0 else self._cols
+        self._k = k
+        self._ctx = None
+        self._on_device = None      # the (U, S, V) objects that the context's factors equal
+
+    def _check_supported(self):
+        if _is_sparse(self.data):
+            raise TypeError("SVD: scipy.sparse data is not supported (dense data only)")
+        if _dist.world().size > 1:
+            raise NotImplementedError("SVD: one rank only (a multi-rank world is not supported)")
+        if min(self._rows, self._cols) > MAX_RANK:
+            raise ValueError("SVD: min(rows, cols) > %d is not supported" % MAX_RANK)
+
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = _lib.Context(_lib.ALGO_PCA, self._rows, self._cols, min(self._rows, self._cols),
+                                     device=_dist.world().local_rank)
+        return self._ctx
+
+    def factorize(self):                                       # svd.py:110-244
+        self._check_supported()
+        arr = np.asarray(self.data[:, :])
+        if arr.dtype == np.float64 and not self.__dict__.get("_warned_f64", False):
+            self._warned_f64 = True
+            warnings.warn("SVD: float64 data is rounded to float32 on the device (the Gram matrix of the rounded data is "
+                          "formed in float64; DESIGN.md 3.14)", PrecisionWarning, stacklevel=2)
+        ctx = self._context()
+        ctx.set_v_dense(arr)
+        rank = ctx.svd_decompose()
+        U, S, V = ctx.svd_get(rank)
+        self.U, self.S, self.V = U, np.diag(S), V
+        self._on_device = (self.U, self.S, self.V)
+
+    def frobenius_norm(self):                                  # svd.py:92-107
+        """||data - U S V||_F of the data that factorize() saw."""
+        self._check_supported()
+        U, S, V = self.U, self.S, self.V                       # AttributeError before factorize(), as in the reference
+        if self._ctx is None:
+            raise AttributeError("SVD.frobenius_norm: factorize() has not run")
+        ctx = self._context()
+        cur = self._on_device
+        if cur is None or U is not cur[0] or S is not cur[1] or V is not cur[2]:
+            # the caller rebound a factor: the device takes W = U and H = S V of the arrays at hand
+            k = ctx.k
+            W = np.zeros((self._rows, k))
+            H = np.zeros((k, self._cols))
+            r = np.asarray(U).shape[1]
+            if r > k:
+                raise ValueError("SVD.frobenius_norm: U has more columns than min(rows, cols)")
+            W[:, :r] = U
+            H[:r] = np.dot(S, V)
+            ctx.set_w(W)
+            ctx.set_h(H)
+            self._on_device = (U, S, V)
+        return ctx.frobenius()
