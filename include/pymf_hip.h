@@ -39,6 +39,8 @@
  *   pmf_cluster_get/set_assigned  self.assigned of Kmeans  pymf/kmeans.py:77 (algo 6)
  *   pmf_sivm_get_select   self.select of SIVM          pymf/sivm.py:145-166,193 (algo 10)
  *   pmf_svd_decompose / pmf_svd_get  SVD.factorize, U / S / V  pymf/svd.py:110-158 (algo 12; PCA: pymf/pca.py)
+ *   pmf_cur_sqnorms       CUR.sample_probability       pymf/cur.py:84-97 (algo 14)
+ *   pmf_cur_compute / pmf_cur_get  CUR.computeUCR, C / U / R  pymf/cur.py:99-120 (CMD: pymf/cmd.py)
  *
  * Every function returns PMF_OK (0) or a negative status and never throws;
  * pmf_last_error() gives a human-readable message for the last failure.
@@ -66,6 +68,7 @@ enum {
 
 enum { PMF_ALGO_NMF = 0, PMF_ALGO_NMFALS = 1, PMF_ALGO_SNMF = 2, PMF_ALGO_BNMF = 3, PMF_ALGO_RNMF = 4, PMF_ALGO_CNMF = 5,
        PMF_ALGO_KMEANS = 6, PMF_ALGO_CMEANS = 8, PMF_ALGO_SIVM = 10, PMF_ALGO_AA = 11, PMF_ALGO_PCA = 12 };   /* 7 and 9 are not assigned: pmf_ctx_create refuses them */
+enum { PMF_ALGO_CUR = 14 };   /* CUR / CMD; 13 is not assigned and refused as well */
 
 /* pmf_factorize flags (the reference's factorize() keyword arguments, nmf.py:141-142) */
 enum { PMF_COMPUTE_W = 1u, PMF_COMPUTE_H = 2u, PMF_COMPUTE_ERR = 4u };
@@ -269,6 +272,24 @@ int pmf_aa_rounds(pmf_ctx* ctx, int32_t* rounds);
 int pmf_svd_decompose(pmf_ctx* ctx, int32_t* rank);
 int pmf_svd_rank(pmf_ctx* ctx, int32_t* rank);
 int pmf_svd_get(pmf_ctx* ctx, double* U, double* S, double* V);
+
+/* CUR / CMD (algo 14; pymf/cur.py, pymf/cmd.py for dense data): data ~ C U R with C = data[:, cid] diag(sqrt(ccnt)),
+ * R = diag(sqrt(rcnt)) data[rid, :] and U = pinv(C) data pinv(R), computed as (C^T C)^+ (C^T data R^T) (R R^T)^+: the two small
+ * Gram matrices and the middle product -- the one pass over the data -- are formed in float64 on the float64 MFMA (k_gram_f64,
+ * k_cross_f64), the pseudo-inverses come from the float64 Jacobi solver with svd.py's cut (eigenvalues <= 1e-8 dropped).  Dense
+ * resident data, one rank, the context's k = max(nr, nc) <= 128 -- PMF_EINVAL otherwise.  There are no W / H steps and no
+ * pmf_factorize with algo 14.  Two runs give the same bits.
+ * pmf_cur_sqnorms: the row sums (row_sq [m]) and column sums (col_sq [n]) of data^2 in float64, one read of V: what
+ * CUR.sample_probability normalises (cur.py:84-97); the draws stay with the caller.  A NULL pointer skips that side.
+ * pmf_cur_compute: CUR.computeUCR (cur.py:99-120) for nr row indices rid with multiplicities rcnt and nc column indices cid with
+ * multiplicities ccnt, 1 <= nr, nc <= min(128, k); a negative index counts from the end (-1 is the last row / column), rcnt or
+ * ccnt NULL means all ones; indices need not be sorted or distinct.  PMF_EINVAL for an index out of range or a count < 1.  It
+ * leaves W = C U and H = R (float32), so that pmf_frobenius is svd.py's ||data - C U R||.
+ * pmf_cur_get: C (m x nc), U (nc x nr) and R (nr x n) of the last pmf_cur_compute as float64, row-major, C and R scaled as
+ * the reference returns them; a NULL pointer skips that factor.  PMF_EINVAL when the resident V has not been decomposed. */
+int pmf_cur_sqnorms(pmf_ctx* ctx, double* row_sq, double* col_sq);
+int pmf_cur_compute(pmf_ctx* ctx, const int32_t* rid, const int32_t* rcnt, int32_t nr, const int32_t* cid, const int32_t* ccnt, int32_t nc);
+int pmf_cur_get(pmf_ctx* ctx, double* C, double* U, double* R);
 
 /* Device time (ms, HIP events on the library's stream) of the last pmf_factorize loop. */
 int pmf_last_loop_ms(pmf_ctx* ctx, double* ms);

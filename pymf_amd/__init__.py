@@ -16,7 +16,10 @@ from .sivm import SIVM        # noqa: F401  
 from .aa import AA            # noqa: F401  
 from .svd import SVD          # noqa: F401  
 from .pca import PCA          # noqa: F401  
+from .svd import pinv         # noqa: F401  (svd.py:27-45)
+from .cur import CUR          # noqa: F401  
+from .cmd import CMD          # noqa: F401  
 from . import dist            # noqa: F401
 
-__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "SVD", "PCA", "dist"]
+__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "SVD", "PCA", "CUR", "CMD", "pinv", "dist"]
 __version__ = "0.1.0"

@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("PMF_LIB") or os.path.join(_HERE, "csrc", "libpymf_hip
 
 PMF_OK, PMF_EINVAL, PMF_EHIP, PMF_ENCCL, PMF_ENOMEM, PMF_ESINGULAR, PMF_ENUMERIC = 0, -1, -2, -3, -4, -5, -6
 ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF, ALGO_KMEANS, ALGO_CMEANS, ALGO_SIVM, ALGO_AA, ALGO_PCA = 0, 1, 2, 3, 4, 5, 6, 8, 10, 11, 12   # (7, 9: not assigned)
+ALGO_CUR = 14   # (13: not assigned)
 COMPUTE_W, COMPUTE_H, COMPUTE_ERR = 1, 2, 4
 STREAM_RESID = 8
 NCCL_ID_BYTES = 128
@@ -71,6 +72,9 @@ SYMBOLS = [
     ("pmf_svd_decompose", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_svd_rank", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_svd_get", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    ("pmf_cur_sqnorms", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p]),
+    ("pmf_cur_compute", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_int32]),
+    ("pmf_cur_get", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     ("pmf_stream_begin", _c.c_int, [_ctx, _c.c_uint32, _c.c_int64]),
     ("pmf_stream_tile", _c.c_int, [_ctx, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64]),
     ("pmf_stream_end", _c.c_int, [_ctx, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int32)]),
@@ -415,6 +419,31 @@ class Context(object):
         V = np.zeros((rank, self.n), dtype=np.float64) if "V" in want else None
         self._chk(self._lib.pmf_svd_get(self._h, *(None if a is None else a.ctypes.data for a in (U, S, V))))
         return U, S, V
+
+    def cur_sqnorms(self):
+        """CUR / CMD: the row sums (m) and column sums (n) of data**2, float64 (pmf_cur_sqnorms)."""
+        row, col = np.zeros(self.m, dtype=np.float64), np.zeros(self.n, dtype=np.float64)
+        self._chk(self._lib.pmf_cur_sqnorms(self._h, row.ctypes.data, col.ctypes.data))
+        return row, col
+
+    def cur_compute(self, rid, rcnt, cid, ccnt):
+        """CUR / CMD: computeUCR for the row indices `rid` with multiplicities `rcnt` and the column indices `cid` with
+        `ccnt` (pmf_cur_compute); negative indices count from the end."""
+        rid, rcnt, cid, ccnt = (np.ascontiguousarray(a, dtype=np.int32) for a in (rid, rcnt, cid, ccnt))
+        assert rid.ndim == 1 and rid.shape == rcnt.shape and cid.ndim == 1 and cid.shape == ccnt.shape
+        self._chk(self._lib.pmf_cur_compute(self._h, rid.ctypes.data, rcnt.ctypes.data, rid.shape[0],
+                                            cid.ctypes.data, ccnt.ctypes.data, cid.shape[0]))
+        self._cur_shape = (int(rid.shape[0]), int(cid.shape[0]))
+
+    def cur_get(self, want="CUR"):
+        """CUR / CMD: C (m x nc), U (nc x nr) and R (nr x n) of the last cur_compute, float64 (pmf_cur_get).  Factors not
+        named in `want` come back as None."""
+        nr, nc = self._cur_shape
+        C = np.zeros((self.m, nc), dtype=np.float64) if "C" in want else None
+        U = np.zeros((nc, nr), dtype=np.float64) if "U" in want else None
+        R = np.zeros((nr, self.n), dtype=np.float64) if "R" in want else None
+        self._chk(self._lib.pmf_cur_get(self._h, *(None if a is None else a.ctypes.data for a in (C, U, R))))
+        return C, U, R
 
     def get_h64(self):
         H = np.empty((self.k, self.n), dtype=np.float64)

@@ -39,6 +39,7 @@
 #include "pmf_sivm.h"
 #include "pmf_aa.h"
 #include "pmf_svd.h"
+#include "pmf_cur.h"
 
 // the internal host code, by concern (each header: one anonymous-namespace block; the order is the dependency order)
 #include "pmf_host_ctx.h"
@@ -56,6 +57,7 @@
 #include "pmf_host_sivm.h"
 #include "pmf_host_aa.h"
 #include "pmf_host_svd.h"
+#include "pmf_host_cur.h"
 #include "pmf_host_factorize.h"
 
 // =============================================================================================
@@ -82,8 +84,8 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                    int32_t rank, int32_t nranks, const void* nccl_id) {
   if (!out) return fail(nullptr, PMF_EINVAL, "out is NULL");
   *out = nullptr;
-  if (algo < 0 || algo > 12 || algo == 7 || algo == 9)
-    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans), 8 (Cmeans), 10 (SIVM), 11 (AA) or 12 (PCA / SVD)");
+  if (algo < 0 || algo > 14 || algo == 7 || algo == 9 || algo == 13)
+    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans), 8 (Cmeans), 10 (SIVM), 11 (AA), 12 (PCA / SVD) or 14 (CUR / CMD)");
   if (m_local < 1 || n < 1 || k < 1) return fail(nullptr, PMF_EINVAL, "m, n, k must be >= 1");
   if (algo == PMF_ALGO_CNMF) {  // C = V^T V is n x n float64 (128 MiB at the limit); the k x k factors on one float64 MFMA tile row
     if (n > 4096) return fail(nullptr, PMF_EINVAL, "CNMF: n (samples) > 4096 is not supported by this build");
@@ -113,6 +115,10 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
     if (k < std::min<int64_t>(m_local, n))
       return fail(nullptr, PMF_EINVAL, "PCA / SVD: the context's base count must be at least min(rows, cols) (the largest possible rank)");
     if (nranks > 1) return fail(nullptr, PMF_EINVAL, "PCA / SVD: one rank only in this build");
+  }
+  if (algo == PMF_ALGO_CUR) {   // the sampled rows and columns are two 64-wide tiles of k_cross_f64 and one 128-wide block of W and H
+    if (k > PMF_CUR_MAX_RANK) return fail(nullptr, PMF_EINVAL, "CUR / CMD: more than 128 sampled rows or columns are not supported by this build");
+    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "CUR / CMD: one rank only in this build");
   }
   // The reference has no limit on num_bases (nmf.py:116-120); the generic kernels beyond 128 bases have been checked against
   // the float64 oracles at 1 500, 2 304 and 2 432 bases (tests/sweeps/bigk_limit_probe.py, tests/test_gpu_bigk.py); beyond 2 432 (19 blocks of 128)
@@ -233,6 +239,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
   if (algo == PMF_ALGO_SIVM) c->path = "sivm_panels";
   if (algo == PMF_ALGO_AA) c->path = "aa_pricing";
   if (algo == PMF_ALGO_PCA) c->path = "svd_gram_f64";
+  if (algo == PMF_ALGO_CUR) c->path = "cur_cross_f64";
   choose_stat_site(c, false);
   *out = c;
   return PMF_OK;
@@ -474,6 +481,7 @@ int pmf_update_w(pmf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
   }
+  if (c && c->algo == PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "CUR / CMD: no W step (pmf_cur_compute is the decomposition)");
   if (c && c->algo == PMF_ALGO_PCA) {                  // (the decomposition reads the data alone: pca.py:93-108)
     PMFCHK(need(c, true, false, false));
     PMFCHK(pca_update_w(c));
@@ -508,6 +516,7 @@ int pmf_update_h(pmf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
   }
+  if (c && c->algo == PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "CUR / CMD: no H step (pmf_cur_compute is the decomposition)");
   if (c && c->algo == PMF_ALGO_PCA) {                  // pca.py:90-91
     PMFCHK(need(c, true, true, false));
     PMFCHK(pca_update_h(c));
@@ -526,7 +535,7 @@ int pmf_frobenius(pmf_ctx* c, double* out) {
     PMFCHK(cnmf_ready(c));
     return cnmf_error(c, false, out);
   }
-  if (is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA) return frobenius_direct(c, out);
+  if (is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA || c->algo == PMF_ALGO_CUR) return frobenius_direct(c, out);
   if (c->algo == PMF_ALGO_PCA) return pca_error(c, out);
   PMFCHK(do_frobenius(c, out));
   return ipc_check(c);
@@ -535,6 +544,7 @@ int pmf_frobenius(pmf_ctx* c, double* out) {
 int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, double* ferr,
                   int32_t* iters_done, int32_t* converged_at) {
   const bool cw = flags & PMF_COMPUTE_W, ch = flags & PMF_COMPUTE_H, ce = flags & PMF_COMPUTE_ERR;
+  if (c && c->algo == PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "CUR / CMD: no iteration (pmf_cur_compute is the decomposition)");
   if (c && (c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_PCA)) PMFCHK(need(c, true, !cw, !ch));   // (either step writes its factor from scratch)
   else if (c && c->algo == PMF_ALGO_AA) PMFCHK(need(c, true, !cw, cw || !ch));   // (the W step reads H, the H step W)
   else PMFCHK(need(c, true, true, true));
@@ -622,6 +632,24 @@ int pmf_svd_get(pmf_ctx* c, double* U, double* S, double* V) {
   return svd_get(c, U, S, V);
 }
 
+int pmf_cur_sqnorms(pmf_ctx* c, double* row_sq, double* col_sq) {
+  if (c && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_cur_sqnorms: CUR / CMD contexts only");
+  PMFCHK(need(c, true, false, false));
+  return cur_sqnorms(c, row_sq, col_sq);
+}
+
+int pmf_cur_compute(pmf_ctx* c, const int32_t* rid, const int32_t* rcnt, int32_t nr, const int32_t* cid, const int32_t* ccnt, int32_t nc) {
+  if (c && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_cur_compute: CUR / CMD contexts only");
+  PMFCHK(need(c, true, false, false));
+  return cur_compute(c, rid, rcnt, nr, cid, ccnt, nc);
+}
+
+int pmf_cur_get(pmf_ctx* c, double* C, double* U, double* R) {
+  if (c && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_cur_get: CUR / CMD contexts only");
+  PMFCHK(need(c, true, false, false));
+  return cur_get(c, C, U, R);
+}
+
 int pmf_cluster_set_assigned(pmf_ctx* c, const int32_t* assigned) {
   if (!c || !assigned) return fail(c, PMF_EINVAL, "pmf_cluster_set_assigned: bad arguments");
   if (c->algo != PMF_ALGO_KMEANS) return fail(c, PMF_EINVAL, "pmf_cluster_set_assigned: Kmeans only");
@@ -695,7 +723,7 @@ int pmf_rnmf_set_s_f32(pmf_ctx* c, const float* S) {
 int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (c) c->hd_synced = false;
   if (!c) return PMF_EINVAL;
-  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA || c->algo == PMF_ALGO_PCA)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
+  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA || c->algo == PMF_ALGO_PCA || c->algo == PMF_ALGO_CUR)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (!c->have_w || !c->have_h) return fail(c, PMF_EINVAL, "pmf_stream_begin: W and H must be set");
   if (max_tile_rows < 1) return fail(c, PMF_EINVAL, "pmf_stream_begin: max_tile_rows must be >= 1");

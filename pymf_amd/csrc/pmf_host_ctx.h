@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_AA, SITE_SVD };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_AA, SITE_SVD, SITE_CUR };
 
 struct KernelStat {
   std::string name = "none";
@@ -186,6 +186,12 @@ struct pmf_ctx {
   bool svd_left = false;        // rows > cols: svd.py's _left_svd
   bool svd_valid = false;       // dSvdE / dSvdS / dSvdP belong to the current V.  <- V
   int pca_bases = 0;            // pmf_set_option("pca_num_bases"): columns of U that PCA's W step takes, 0 = all
+  // CUR / CMD (pmf_cur.h): the unscaled gathers Cg [mp][round_up(nc, 64)] and Rg [round_up(nr, 64)][np] of the last pmf_cur_compute;
+  // on the host sqrt(ccnt), sqrt(rcnt) and the middle factor U [nc][nr]
+  float *dCurCg = nullptr, *dCurRg = nullptr;
+  int cur_nr = 0, cur_nc = 0;
+  std::vector<double> cur_dc, cur_dr, cur_U;
+  bool cur_valid = false;       // they belong to the current V.  <- V
   double lamb_w = 0.0, lamb_h = 0.0;   // BNMF penalty weights (bnmf.py:84-85,118-119)
   // streamed V (pmf_stream_*): row tiles pass through two device buffers, V is never resident
   float* dTile[2] = {nullptr, nullptr};
@@ -388,6 +394,7 @@ void v_replaced(pmf_ctx* c) {
   c->vnorm_valid = c->vnorm_local_valid = c->ps_valid = c->num_valid = c->trace_ready = c->c_valid = false;
   c->cl_sums_valid = c->cl_err_valid = c->cl_mu_valid = false;
   c->svd_valid = false;
+  c->cur_valid = false;
 }
 void w_replaced(pmf_ctx* c, bool by_caller) {   // by_caller: uploaded or filled through the ABI (not the NNDSVD init, not a restored snapshot)
   c->have_w = true; c->ps_valid = c->num_valid = c->trace_ready = c->w_implicit = false;

@@ -1,0 +1,222 @@
+// pmf_host_cur.h -- CUR / CMD: the sampling norms, computeUCR (cur.py:99-120 for dense data) and its factors (kernels: pmf_cur.h, pmf_svd.h)
+// Host code of libpymf_hip.so: included by pmf_api.hip (the translation unit) in this order, nothing else includes it.
+#pragma once
+
+namespace {
+
+int cur_check(pmf_ctx* c, const char* who) {
+  if (c->v_csr || !c->dV) return fail(c, PMF_EINVAL, std::string(who) + ": dense resident data only");
+  if (multi_rank(c)) return fail(c, PMF_EINVAL, std::string(who) + ": one rank only in this build");
+  return PMF_OK;
+}
+
+// cur.py:84-97 without the normalisation: the row sums (m) and column sums (n) of data^2 in float64, one read of V
+int cur_sqnorms(pmf_ctx* c, double* row_sq, double* col_sq) {
+  PMFCHK(cur_check(c, "pmf_cur_sqnorms"));
+  const int64_t mp = c->mp, np = c->np;
+  const int npanels = (int)((np + PMF_CUR_PANEL - 1) / PMF_CUR_PANEL), nblocks = (int)(mp / 64);
+  DevTemps tmp;
+  double *rowpart = nullptr, *colpart = nullptr, *out = nullptr;
+  PMFCHK(talloc(c, tmp, &rowpart, (size_t)npanels * mp));
+  PMFCHK(talloc(c, tmp, &colpart, (size_t)nblocks * np));
+  PMFCHK(talloc(c, tmp, &out, (size_t)(mp + np)));
+  hipLaunchKernelGGL(k_cur_sqnorms, dim3((unsigned)((int64_t)nblocks * npanels)), dim3(256), 0, c->stream, (const float*)c->dV, np, mp, npanels,
+                     rowpart, colpart);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_cur_sqnorms_reduce, dim3((unsigned)((mp + np) / 64)), dim3(1024), 0, c->stream, (const double*)rowpart, npanels, mp,
+                     (const double*)colpart, nblocks, np, out);
+  HIPCHK(c, hipGetLastError());
+  if (row_sq) HIPCHK(c, hipMemcpyAsync(row_sq, out, (size_t)c->m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (col_sq) HIPCHK(c, hipMemcpyAsync(col_sq, out + mp, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
+  return PMF_OK;
+}
+
+// O [TA * 64][TB * 64] float64 = A B^T (A [TA * 64][inner], B [TB * 64][inner]) or A^T B (trans: A [inner][TA * 64], B [inner][TB * 64])
+int cross_f64(pmf_ctx* c, bool trans, const float* A, int64_t lda, int TA, const float* B, int64_t ldb, int TB, int inner, double* O,
+              DevTemps& tmp) {
+  const int ntiles = TA * TB;
+  int nch = 1, cl = inner;
+  svd_chunks(inner, ntiles, &nch, &cl);
+  double* slab = nullptr;
+  PMFCHK(talloc(c, tmp, &slab, (size_t)nch * ntiles * PMF_SVD_TILE * PMF_SVD_TILE));
+  const dim3 grid((unsigned)ntiles, (unsigned)nch);
+  stat_begin(c, SITE_CUR);
+  if (trans) hipLaunchKernelGGL(k_cross_f64<true>, grid, dim3(256), 0, c->stream, A, lda, B, ldb, inner, cl, TB, slab);
+  else hipLaunchKernelGGL(k_cross_f64<false>, grid, dim3(256), 0, c->stream, A, lda, B, ldb, inner, cl, TB, slab);
+  stat_end(c, SITE_CUR);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_cross_reduce_f64, dim3((unsigned)ntiles * 64u), dim3(1024), 0, c->stream, (const double*)slab, nch, ntiles, TB, O,
+                     (int64_t)TB * PMF_SVD_TILE);
+  HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+// P [q][q] (host, row-major) = the pseudo-inverse of diag(d) X diag(d), X = the Gram matrix of the float32 G on the device
+// (G [inner][qp], trans; or G [qp][inner]): float64 Gram matrix, scaled, float64 Jacobi, eigenvalues <= 1e-8 dropped
+// (svd.py:116-117,141-142 as pinv sees them, svd.py:27-45), the rest taken in descending order: P = sum_j e_j e_j^T / lambda_j
+int cur_gram_pinv(pmf_ctx* c, const float* G, int64_t ldg, int q, int qp, int inner, bool trans, const std::vector<double>& d,
+                  std::vector<double>& P) {
+  const int nj = q + (q & 1);
+  DevTemps tmp;
+  double *A = nullptr, *A2 = nullptr, *QT = nullptr, *evals = nullptr, *dd = nullptr;
+  int* info = nullptr;
+  PMFCHK(talloc(c, tmp, &A, (size_t)qp * qp));
+  PMFCHK(talloc(c, tmp, &A2, (size_t)qp * qp));
+  PMFCHK(talloc(c, tmp, &QT, (size_t)qp * qp));
+  PMFCHK(talloc(c, tmp, &evals, (size_t)qp));
+  PMFCHK(talloc(c, tmp, &dd, (size_t)qp));
+  PMFCHK(talloc(c, tmp, &info, 2));
+  HIPCHK(c, hipMemcpyAsync(dd, d.data(), (size_t)q * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  PMFCHK(gram_f64(c, G, ldg, qp, inner, trans, A, tmp));
+  hipLaunchKernelGGL(k_cur_scale_sym, dim3((unsigned)((q * q + 255) / 256)), dim3(256), 0, c->stream, A, qp, q, (const double*)dd);
+  HIPCHK(c, hipGetLastError());
+  PMFCHK(jacobi_eigh_dev(c, A, A2, QT, qp, nj, evals, info));
+  std::vector<double> ev((size_t)nj), E((size_t)nj * qp);
+  HIPCHK(c, hipMemcpyAsync(ev.data(), evals, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(E.data(), QT, E.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
+  std::vector<int> ord;
+  for (int j = 0; j < nj; ++j)
+    if (ev[(size_t)j] > 1e-8) ord.push_back(j);
+  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return ev[(size_t)a] > ev[(size_t)b]; });
+  P.assign((size_t)q * q, 0.0);
+  for (int j : ord) {
+    const double* e = E.data() + (size_t)j * qp;
+    const double inv = 1.0 / ev[(size_t)j];
+    for (int a = 0; a < q; ++a) {
+      const double ea = e[a] * inv;
+      for (int b = 0; b < q; ++b) P[(size_t)a * q + b] += ea * e[b];
+    }
+  }
+  return PMF_OK;
+}
+
+int cur_alloc(pmf_ctx* c) {
+  if (c->dCurCg) return PMF_OK;
+  const int64_t wp = round_up(c->k, 64);              // nr, nc <= k
+  PMFCHK(dalloc(c, &c->dCurCg, (size_t)(c->mp * wp)));
+  PMFCHK(dalloc(c, &c->dCurRg, (size_t)(wp * c->np)));
+  return PMF_OK;
+}
+
+// index list of the ABI -> the device's: negative indices count from the end (-1 is the last), counts default to 1
+int cur_indices(pmf_ctx* c, const int32_t* id, const int32_t* cnt, int n, int64_t extent, std::vector<int>& idx, std::vector<double>& d) {
+  idx.resize((size_t)n);
+  d.resize((size_t)n);
+  for (int q = 0; q < n; ++q) {
+    const int64_t v = id[q] < 0 ? (int64_t)id[q] + extent : (int64_t)id[q];
+    if (v < 0 || v >= extent) return fail(c, PMF_EINVAL, "pmf_cur_compute: index out of range");
+    if (cnt && cnt[q] < 1) return fail(c, PMF_EINVAL, "pmf_cur_compute: a count must be >= 1");
+    idx[(size_t)q] = (int)v;
+    d[(size_t)q] = std::sqrt((double)(cnt ? cnt[q] : 1));
+  }
+  return PMF_OK;
+}
+
+// cur.py:99-120 on the resident V: C = data[:, cid] diag(sqrt(ccnt)), R = diag(sqrt(rcnt)) data[rid, :],
+// U = pinv(C) data pinv(R) = (C^T C)^+ (dc o (Cg^T data Rg^T) o dr) (R R^T)^+ (pmf_cur.h).  The data are read once by k_cross_f64:
+// rows <= cols: T [mp][rp] = V Rg^T, then M = Cg^T T; otherwise T' [cp][np] = Cg^T V, then M = T' Rg^T (float64 MFMA, dgemm64).
+// The c x r sized rest runs on the host in float64 in a fixed order.  Leaves W = C U and H = R, so that pmf_frobenius is
+// ||data - C U R|| (svd.py:92-107).
+int cur_compute(pmf_ctx* c, const int32_t* rid, const int32_t* rcnt, int nr, const int32_t* cid, const int32_t* ccnt, int nc) {
+  PMFCHK(cur_check(c, "pmf_cur_compute"));
+  if (!rid || !cid) return fail(c, PMF_EINVAL, "pmf_cur_compute: rid and cid must not be NULL");
+  const int lim = std::min(c->k, PMF_CUR_MAX_RANK);
+  if (nr < 1 || nc < 1 || nr > lim || nc > lim)
+    return fail(c, PMF_EINVAL, "pmf_cur_compute: 1 <= nr, nc <= min(128, the context's k) rows and columns");
+  std::vector<int> hr, hc;
+  std::vector<double> dr, dc;
+  PMFCHK(cur_indices(c, rid, rcnt, nr, c->m, hr, dr));
+  PMFCHK(cur_indices(c, cid, ccnt, nc, c->n, hc, dc));
+  c->cur_valid = false;
+  PMFCHK(cur_alloc(c));
+  const int64_t mp = c->mp;
+  const int np = c->np, cp = (int)round_up(nc, 64), rp = (int)round_up(nr, 64), KP = c->KP;
+  const bool trans = c->m > c->n;
+  std::vector<double> M((size_t)cp * rp);
+  {
+    DevTemps tmp;
+    int *dcid = nullptr, *drid = nullptr;
+    double *side = nullptr, *T = nullptr, *dM = nullptr;
+    PMFCHK(talloc(c, tmp, &dcid, (size_t)nc));
+    PMFCHK(talloc(c, tmp, &drid, (size_t)nr));
+    PMFCHK(talloc(c, tmp, &side, trans ? (size_t)rp * np : (size_t)cp * mp));       // Rd [rp][np] or CgT [cp][mp]
+    PMFCHK(talloc(c, tmp, &T, trans ? (size_t)cp * np : (size_t)mp * rp));
+    PMFCHK(talloc(c, tmp, &dM, (size_t)cp * rp));
+    HIPCHK(c, hipMemcpyAsync(dcid, hc.data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(drid, hr.data(), (size_t)nr * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    // (the gathers take the leading dimensions of this call: Cg [mp][cp], Rg [rp][np], both within the buffers of cur_alloc)
+    hipLaunchKernelGGL(k_cur_gather, dim3(elem_grid(mp * cp + (int64_t)rp * np)), dim3(256), 0, c->stream, (const float*)c->dV, mp, np,
+                       (const int*)dcid, nc, cp, (const int*)drid, nr, rp, c->dCurCg, c->dCurRg, trans ? (double*)nullptr : side,
+                       trans ? side : (double*)nullptr);
+    HIPCHK(c, hipGetLastError());
+    if (trans) {
+      PMFCHK(cross_f64(c, true, c->dCurCg, cp, cp / 64, c->dV, np, np / 64, (int)mp, T, tmp));
+      PMFCHK(dgemm64(c, T, np, side, np, np, dM, rp, cp, rp, true));
+    } else {
+      PMFCHK(cross_f64(c, false, c->dV, np, (int)(mp / 64), c->dCurRg, np, rp / 64, np, T, tmp));
+      PMFCHK(dgemm64(c, side, mp, T, rp, (int)mp, dM, rp, cp, rp, false));
+    }
+    HIPCHK(c, hipMemcpyAsync(M.data(), dM, M.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // the temporaries are released at the end of the block
+  }
+  std::vector<double> Pc, Pr;
+  PMFCHK(cur_gram_pinv(c, c->dCurCg, cp, nc, cp, (int)mp, true, dc, Pc));
+  PMFCHK(cur_gram_pinv(c, c->dCurRg, np, nr, rp, np, false, dr, Pr));
+  // U = Pc (dc o M o dr) Pr
+  std::vector<double> X((size_t)nc * nr, 0.0), U((size_t)nc * nr, 0.0), Us((size_t)nc * nr);
+  for (int a = 0; a < nc; ++a)
+    for (int q = 0; q < nc; ++q) {
+      const double p = Pc[(size_t)a * nc + q] * dc[(size_t)q];
+      for (int b = 0; b < nr; ++b) X[(size_t)a * nr + b] += p * (M[(size_t)q * rp + b] * dr[(size_t)b]);
+    }
+  for (int a = 0; a < nc; ++a)
+    for (int q = 0; q < nr; ++q) {
+      const double x = X[(size_t)a * nr + q];
+      for (int b = 0; b < nr; ++b) U[(size_t)a * nr + b] += x * Pr[(size_t)q * nr + b];
+    }
+  for (int a = 0; a < nc; ++a)
+    for (int b = 0; b < nr; ++b) Us[(size_t)a * nr + b] = dc[(size_t)a] * U[(size_t)a * nr + b];
+  {
+    DevTemps tmp;
+    double *dUs = nullptr, *ddr = nullptr;
+    PMFCHK(talloc(c, tmp, &dUs, Us.size()));
+    PMFCHK(talloc(c, tmp, &ddr, (size_t)nr));
+    HIPCHK(c, hipMemcpyAsync(dUs, Us.data(), Us.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ddr, dr.data(), (size_t)nr * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_cur_factors, dim3(elem_grid(mp * KP + (int64_t)KP * np)), dim3(256), 0, c->stream, (const float*)c->dCurCg, cp, nc,
+                       (const double*)dUs, nr, c->m, mp, KP, (const float*)c->dCurRg, np, (const double*)ddr, c->dW, c->dH);
+    HIPCHK(c, hipGetLastError());
+    w_replaced(c, false);
+    h_replaced(c, false, true);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  c->cur_nr = nr; c->cur_nc = nc;
+  c->cur_dr = dr; c->cur_dc = dc; c->cur_U = U;
+  c->cur_valid = true;
+  return PMF_OK;
+}
+
+// C (rows x nc), U (nc x nr) and R (nr x cols) of the last cur_compute as float64, row-major; any of them may be null
+int cur_get(pmf_ctx* c, double* C, double* U, double* R) {
+  if (!c->cur_valid) return fail(c, PMF_EINVAL, "pmf_cur_get: no decomposition of the current data (pmf_cur_compute first)");
+  const int nr = c->cur_nr, nc = c->cur_nc, cp = (int)round_up(nc, 64);
+  const int64_t m = c->m, n = c->n;
+  if (U) std::memcpy(U, c->cur_U.data(), (size_t)nc * nr * sizeof(double));
+  std::vector<float> Cg, Rg;
+  if (C) {
+    Cg.resize((size_t)m * cp);
+    HIPCHK(c, hipMemcpyAsync(Cg.data(), c->dCurCg, Cg.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (R) {
+    Rg.resize((size_t)nr * c->np);
+    HIPCHK(c, hipMemcpyAsync(Rg.data(), c->dCurRg, Rg.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (C) for (int64_t row = 0; row < m; ++row) for (int j = 0; j < nc; ++j) C[(size_t)row * nc + j] = (double)Cg[(size_t)row * cp + j] * c->cur_dc[(size_t)j];
+  if (R) for (int i = 0; i < nr; ++i) for (int64_t col = 0; col < n; ++col) R[(size_t)i * n + col] = c->cur_dr[(size_t)i] * (double)Rg[(size_t)i * c->np + col];
+  return PMF_OK;
+}
+
+}  // namespace

@@ -12,9 +12,9 @@ void svd_chunks(int inner, int ntiles, int* nchunks, int* chunk_len) {
   *nchunks = (inner + *chunk_len - 1) / *chunk_len;
 }
 
-// A [qp][qp] float64 = V V^T (q = mp) or V^T V (trans: q = np) of the resident dense V
-int gram_f64(pmf_ctx* c, bool trans, double* A, DevTemps& tmp) {
-  const int qp = trans ? c->np : (int)c->mp, inner = trans ? (int)c->mp : c->np;
+// A [qp][qp] float64 = X X^T (X [qp][inner]) or X^T X (trans: X [inner][qp]) of the float32 X with leading dimension ldx, zero
+// padded; qp and inner are multiples of 64
+int gram_f64(pmf_ctx* c, const float* X, int64_t ldx, int qp, int inner, bool trans, double* A, DevTemps& tmp) {
   const int T = qp / PMF_SVD_TILE, ntiles = T * (T + 1) / 2;
   int nch = 1, cl = inner;
   svd_chunks(inner, ntiles, &nch, &cl);
@@ -22,8 +22,8 @@ int gram_f64(pmf_ctx* c, bool trans, double* A, DevTemps& tmp) {
   PMFCHK(talloc(c, tmp, &slab, (size_t)nch * ntiles * PMF_SVD_TILE * PMF_SVD_TILE));
   const dim3 grid((unsigned)ntiles, (unsigned)nch);
   stat_begin(c, SITE_SVD);
-  if (trans) hipLaunchKernelGGL(k_gram_f64<true>, grid, dim3(256), 0, c->stream, (const float*)c->dV, (int64_t)c->np, inner, cl, T, slab);
-  else hipLaunchKernelGGL(k_gram_f64<false>, grid, dim3(256), 0, c->stream, (const float*)c->dV, (int64_t)c->np, inner, cl, T, slab);
+  if (trans) hipLaunchKernelGGL(k_gram_f64<true>, grid, dim3(256), 0, c->stream, X, ldx, inner, cl, T, slab);
+  else hipLaunchKernelGGL(k_gram_f64<false>, grid, dim3(256), 0, c->stream, X, ldx, inner, cl, T, slab);
   stat_end(c, SITE_SVD);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_gram_reduce_f64, dim3((unsigned)ntiles * 64u), dim3(1024), 0, c->stream, (const double*)slab, nch, ntiles, T, A, (int64_t)qp);
@@ -65,7 +65,7 @@ int svd_dense(pmf_ctx* c) {
   PMFCHK(talloc(c, tmp, &info, 2));
   PMFCHK(talloc(c, tmp, &order, (size_t)KP));
   if (left) PMFCHK(talloc(c, tmp, &B, (size_t)KP * qp));
-  PMFCHK(gram_f64(c, left, A, tmp));
+  PMFCHK(gram_f64(c, c->dV, (int64_t)c->np, qp, left ? (int)c->mp : c->np, left, A, tmp));
   PMFCHK(jacobi_eigh_dev(c, A, A2, QT, qp, nj, evals, info));
   std::vector<double> ev((size_t)nj);
   HIPCHK(c, hipMemcpyAsync(ev.data(), evals, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, c->stream));

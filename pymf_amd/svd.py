@@ -8,8 +8,10 @@ float64 Jacobi solver, and the projected side is multiplied in float32 (DESIGN.m
 and V (r x cols) come back as float64 arrays, as the reference returns them; r is the number of eigenvalues kept.
 
 Supported: dense data, one rank, min(rows, cols) <= 2432.  scipy.sparse data raises TypeError, a multi-rank world
-NotImplementedError, a larger short side ValueError.  `k` is accepted and ignored for dense data, as in svd.py.  There is
-no `pinv` yet.
+NotImplementedError, a larger short side ValueError.  `k` is accepted and ignored for dense data, as in svd.py.
+
+`pinv(A, k=-1, eps=1e-8)` is svd.py:27-45: SVD(A).factorize(), the reciprocals of the singular values above `eps`, then
+V^T diag U^T on the host arrays that SVD returns; it has SVD's limits.
 """
 import warnings
 
@@ -19,9 +21,18 @@ from . import _lib
 from . import dist as _dist
 from .nmf import PrecisionWarning, _is_sparse
 
-__all__ = ["SVD"]
+__all__ = ["SVD", "pinv"]
 
 MAX_RANK = 2432   # PMF_SVD_MAX_RANK (pmf_svd.h)
+
+
+def pinv(A, k=-1, eps=10 ** -8):                               # svd.py:27-45
+    """Pseudo-inverse of the dense matrix A through SVD(A): V^T diag(1 / s_i for s_i > eps) U^T, float64."""
+    svd_mdl = SVD(A, k=k)
+    svd_mdl.factorize()
+    s = svd_mdl.S.diagonal()
+    inv = np.where(s > eps, 1.0 / np.where(s > eps, s, 1.0), 0.0)
+    return np.dot(svd_mdl.V.T, inv[:, np.newaxis] * svd_mdl.U.T)
 
 
 class SVD(object):
