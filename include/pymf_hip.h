@@ -254,7 +254,7 @@ int pmf_aa_rounds(pmf_ctx* ctx, int32_t* rounds);
 
 /* PCA / SVD (algo 12; pymf/svd.py:110-158 for dense data, pymf/pca.py): the SVD of the resident V through the eigen-decomposition
  * of its Gram matrix on the short side -- V^T V for rows > cols (_left_svd), V V^T otherwise (_right_svd) -- formed in float64
- * on the float64 MFMA (k_gram_f64), decomposed by the float64 Jacobi solver of pmf_nndsvd_init.  Eigenvalues <= 1e-8 are dropped
+ * on the float64 MFMA (k_prod_f64, upper block triangle), decomposed by the float64 Jacobi solver of pmf_nndsvd_init.  Eigenvalues <= 1e-8 are dropped
  * as in svd.py, the rest sorted descending; the side that comes from the eigenvectors is float64, the projected side
  * (U = data V^T S^-1 or V = S^-1 U^T data) is multiplied in float32.  Dense resident data, one rank, min(rows, cols) <= 2432,
  * and the context's k >= min(rows, cols) (the largest possible rank; W and H are k wide) -- pmf_ctx_create returns PMF_EINVAL
@@ -275,8 +275,8 @@ int pmf_svd_get(pmf_ctx* ctx, double* U, double* S, double* V);
 
 /* CUR / CMD (algo 14; pymf/cur.py, pymf/cmd.py for dense data): data ~ C U R with C = data[:, cid] diag(sqrt(ccnt)),
  * R = diag(sqrt(rcnt)) data[rid, :] and U = pinv(C) data pinv(R), computed as (C^T C)^+ (C^T data R^T) (R R^T)^+: the two small
- * Gram matrices and the middle product -- the one pass over the data -- are formed in float64 on the float64 MFMA (k_gram_f64,
- * k_cross_f64), the pseudo-inverses come from the float64 Jacobi solver with svd.py's cut (eigenvalues <= 1e-8 dropped).  Dense
+ * Gram matrices and the middle product -- the one pass over the data -- are formed in float64 on the float64 MFMA (one kernel,
+ * k_prod_f64, with two tile maps), the pseudo-inverses come from the float64 Jacobi solver with svd.py's cut (eigenvalues <= 1e-8 dropped).  Dense
  * resident data, one rank, the context's k = max(nr, nc) <= 128 -- PMF_EINVAL otherwise.  There are no W / H steps and no
  * pmf_factorize with algo 14.  Two runs give the same bits.
  * pmf_cur_sqnorms: the row sums (row_sq [m]) and column sums (col_sq [n]) of data^2 in float64, one read of V: what

@@ -116,7 +116,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
       return fail(nullptr, PMF_EINVAL, "PCA / SVD: the context's base count must be at least min(rows, cols) (the largest possible rank)");
     if (nranks > 1) return fail(nullptr, PMF_EINVAL, "PCA / SVD: one rank only in this build");
   }
-  if (algo == PMF_ALGO_CUR) {   // the sampled rows and columns are two 64-wide tiles of k_cross_f64 and one 128-wide block of W and H
+  if (algo == PMF_ALGO_CUR) {   // the sampled rows and columns are two 64-wide tiles of k_prod_f64 and one 128-wide block of W and H
     if (k > PMF_CUR_MAX_RANK) return fail(nullptr, PMF_EINVAL, "CUR / CMD: more than 128 sampled rows or columns are not supported by this build");
     if (nranks > 1) return fail(nullptr, PMF_EINVAL, "CUR / CMD: one rank only in this build");
   }

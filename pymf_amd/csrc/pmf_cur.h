@@ -1,17 +1,18 @@
 // pmf_cur.h -- CUR / CMD (pymf/cur.py, pymf/cmd.py): the sampling norms of the resident float32 V, the gather of the chosen
-// columns and rows, and the one product that touches the whole data, T = V Rg^T or T' = Cg^T V, in float64.
+// columns and rows, and the factors.  The one product that touches the whole data, T = V Rg^T or T' = Cg^T V, is k_prod_f64 of
+// pmf_svd.h on the full tile grid.
 //
 // cur.py:99-120 computes U = pinv(C) data pinv(R) with C = data[:, cid] diag(sqrt(ccnt)), R = diag(sqrt(rcnt)) data[rid, :].
 // With Cg, Rg the unscaled gathers and dc = sqrt(ccnt), dr = sqrt(rcnt) this is
 //   U = (C^T C)^+ (dc o (Cg^T data Rg^T) o dr) (R R^T)^+ ,   C^T C = dc dc^T o (Cg^T Cg),   R R^T = dr dr^T o (Rg Rg^T).
-// A pseudo-inverse sits on either side of the middle product, so it is formed as the Gram matrices of pmf_svd.h are: operands
+// A pseudo-inverse sits on either side of the middle product, so it is formed by the kernel of the Gram matrices: operands
 // widened on load (exact), products (exact: 48 bits) and sums on the float64 MFMA, the chunks of the inner dimension added in a
 // fixed order.  A float32 middle product is off by 2e-5 ... 2e-3 of max |U| on well-conditioned cases already.
 #pragma once
 #include "pmf_dev.h"
 #include "pmf_svd.h"
 
-constexpr int PMF_CUR_MAX_RANK = 128;       // rows / columns sampled: two 64-wide tiles of k_cross_f64, one KP = 128 block of W and H
+constexpr int PMF_CUR_MAX_RANK = 128;       // rows / columns sampled: two 64-wide tiles of k_prod_f64, one KP = 128 block of W and H
 constexpr int PMF_CUR_PANEL = 256;          // columns a workgroup of k_cur_sqnorms owns (four 64-column sub-panels)
 
 // Row and column sums of squares of V [mp][ld] float32 (zero padded), float64.  grid = blocks of 64 rows x npanels panels of 256
@@ -69,29 +70,16 @@ __global__ __launch_bounds__(256) void k_cur_sqnorms(const float* __restrict__ V
   if (t < 64 * nsub) colpart[(int64_t)rblk * ld + c0 + t] = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
 }
 
-// out [mp + ld]: the row sums (over the npanels partials of rowpart), then the column sums (over the nblocks partials of colpart).
-// 64 outputs per workgroup of 1024 threads: wave w adds partials w, w + 16, ..., the 16 sums are combined in wave order
-// (as k_gram_reduce_f64).  grid = (mp + ld) / 64.
+// out [mp + ld]: the row sums (over the npanels partials of rowpart), then the column sums (over the nblocks partials of colpart),
+// each in the fixed order of sum_partials16 (pmf_svd.h).  64 outputs per workgroup of 1024 threads, grid = (mp + ld) / 64.
 __global__ __launch_bounds__(1024) void k_cur_sqnorms_reduce(const double* __restrict__ rowpart, int npanels, int64_t mp,
                                                              const double* __restrict__ colpart, int nblocks, int64_t ld,
                                                              double* __restrict__ out) {
   __shared__ double part[16][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t e = (int64_t)blockIdx.x * 64 + lane;
+  const int64_t e = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
   const bool row = e < mp;
-  const double* p = row ? rowpart + e : colpart + (e - mp);
-  const int64_t stride = row ? mp : ld;
-  const int cnt = row ? npanels : nblocks;
-  double s = 0.0;
-  for (int q = wv; q < cnt; q += 16) s += p[q * stride];
-  part[wv][lane] = s;
-  __syncthreads();
-  if (wv == 0) {
-    double tot = part[0][lane];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) tot += part[w][lane];
-    out[e] = tot;
-  }
+  const double tot = sum_partials16(row ? rowpart + e : colpart + (e - mp), row ? mp : ld, row ? npanels : nblocks, part);
+  if (threadIdx.x < 64) out[e] = tot;
 }
 
 // The chosen columns and rows of V [mp][np], unscaled: Cg [mp][cp] (column j = column cid[j] of V, columns >= nc zero) and
@@ -115,93 +103,6 @@ __global__ __launch_bounds__(256) void k_cur_gather(const float* __restrict__ V,
       Rg[q] = v;
       if (Rd) Rd[q] = (double)v;
     }
-  }
-}
-
-// Partial 64 x 64 tile of the two-operand sibling of k_gram_f64 (pmf_svd.h), float32 operands widened on load:
-//   TRANS = false: O [ra][rb] = sum_k A[ra][k] B[rb][k]   (T = V Rg^T: A = V, B = Rg, both contiguous along k)
-//   TRANS = true:  O [ra][rb] = sum_k A[k][ra] B[k][rb]   (T' = Cg^T V: A = Cg, B = V; the 16 lanes of one MFMA row read 16
-//                                                          adjacent columns of row k)
-// grid = (TA * TB tiles of the full tile grid, tile = ta * TB + tb; chunks of the inner dimension), 256 threads: wave w owns rows
-// 16 w .. 16 w + 15 of the tile, four 16 x 16 accumulators (the four column blocks).  Operand order, fetch and C / D layout are
-// k_gram_f64's.  slab [chunk][tile][64][64] float64: no atomics, k_cross_reduce_f64 adds the chunks in a fixed order.
-// chunk_len and inner are multiples of 64; both operands are zero padded to whole tiles.
-template <bool TRANS>
-__global__ __launch_bounds__(256) void k_cross_f64(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
-                                                   int inner, int chunk_len, int TB, double* __restrict__ slab) {
-  const int ta = (int)blockIdx.x / TB, tb = (int)blockIdx.x % TB;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int i = lane & 15, g = lane >> 4;
-  const int k0 = (int)blockIdx.y * chunk_len;
-  const int k1 = k0 + chunk_len < inner ? k0 + chunk_len : inner;
-  const int ra = ta * PMF_SVD_TILE + wv * 16 + i;     // the A operand's row of the output
-  const int rb = tb * PMF_SVD_TILE + i;               // the B operand's: rb + 16 j
-  f64x4 acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) acc[j] = f64x4{0.0, 0.0, 0.0, 0.0};
-  if constexpr (!TRANS) {
-    const float* ap = A + (int64_t)ra * lda + 4 * g;
-    const float* bp = B + (int64_t)rb * ldb + 4 * g;
-    for (int k = k0; k < k1; k += 32) {
-      f32x4 a[2], b[2][4];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        a[h] = *reinterpret_cast<const f32x4*>(ap + k + 16 * h);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[h][j] = *reinterpret_cast<const f32x4*>(bp + (int64_t)(16 * j) * ldb + k + 16 * h);
-      }
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] = mfma_f64((double)a[h][u], (double)b[h][j][u], acc[j]);
-    }
-  } else {
-    const float* ap = A + (int64_t)g * lda + ra;
-    const float* bp = B + (int64_t)g * ldb + rb;
-    for (int k = k0; k < k1; k += 16) {
-      float a[4], b[4][4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        a[s] = ap[(int64_t)(k + 4 * s) * lda];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[s][j] = bp[(int64_t)(k + 4 * s) * ldb + 16 * j];
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = mfma_f64((double)a[s], (double)b[s][j], acc[j]);
-    }
-  }
-  double* o = slab + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (PMF_SVD_TILE * PMF_SVD_TILE);
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o[(wv * 16 + g + 4 * r) * PMF_SVD_TILE + 16 * j + i] = acc[j][r];
-}
-
-// Tile (ta, tb) of O [TA * 64][ld] = the sum of its nchunks partial tiles in a fixed order: k_gram_reduce_f64 on the full tile
-// grid.  grid = ntiles * 64 (64 elements per workgroup), 1024 threads.
-__global__ __launch_bounds__(1024) void k_cross_reduce_f64(const double* __restrict__ slab, int nchunks, int ntiles, int TB,
-                                                           double* __restrict__ O, int64_t ld) {
-  __shared__ double part[16][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int tile = (int)(blockIdx.x >> 6);
-  const int e = (((int)blockIdx.x & 63) << 6) + lane;       // element of the tile
-  const int64_t stride = (int64_t)ntiles * (PMF_SVD_TILE * PMF_SVD_TILE);
-  const double* p = slab + (int64_t)tile * (PMF_SVD_TILE * PMF_SVD_TILE) + e;
-  double s = 0.0;
-#pragma unroll 4
-  for (int ch = wv; ch < nchunks; ch += 16) s += p[ch * stride];
-  part[wv][lane] = s;
-  __syncthreads();
-  if (wv == 0) {
-    double tot = part[0][lane];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) tot += part[w][lane];
-    const int ta = tile / TB, tb = tile % TB;
-    O[((int64_t)ta * PMF_SVD_TILE + (e >> 6)) * ld + tb * PMF_SVD_TILE + (e & 63)] = tot;
   }
 }
 

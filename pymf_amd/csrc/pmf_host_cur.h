@@ -32,54 +32,21 @@ int cur_sqnorms(pmf_ctx* c, double* row_sq, double* col_sq) {
   return PMF_OK;
 }
 
-// O [TA * 64][TB * 64] float64 = A B^T (A [TA * 64][inner], B [TB * 64][inner]) or A^T B (trans: A [inner][TA * 64], B [inner][TB * 64])
-int cross_f64(pmf_ctx* c, bool trans, const float* A, int64_t lda, int TA, const float* B, int64_t ldb, int TB, int inner, double* O,
-              DevTemps& tmp) {
-  const int ntiles = TA * TB;
-  int nch = 1, cl = inner;
-  svd_chunks(inner, ntiles, &nch, &cl);
-  double* slab = nullptr;
-  PMFCHK(talloc(c, tmp, &slab, (size_t)nch * ntiles * PMF_SVD_TILE * PMF_SVD_TILE));
-  const dim3 grid((unsigned)ntiles, (unsigned)nch);
-  stat_begin(c, SITE_CUR);
-  if (trans) hipLaunchKernelGGL(k_cross_f64<true>, grid, dim3(256), 0, c->stream, A, lda, B, ldb, inner, cl, TB, slab);
-  else hipLaunchKernelGGL(k_cross_f64<false>, grid, dim3(256), 0, c->stream, A, lda, B, ldb, inner, cl, TB, slab);
-  stat_end(c, SITE_CUR);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_cross_reduce_f64, dim3((unsigned)ntiles * 64u), dim3(1024), 0, c->stream, (const double*)slab, nch, ntiles, TB, O,
-                     (int64_t)TB * PMF_SVD_TILE);
-  HIPCHK(c, hipGetLastError());
-  return PMF_OK;
-}
-
 // P [q][q] (host, row-major) = the pseudo-inverse of diag(d) X diag(d), X = the Gram matrix of the float32 G on the device
 // (G [inner][qp], trans; or G [qp][inner]): float64 Gram matrix, scaled, float64 Jacobi, eigenvalues <= 1e-8 dropped
 // (svd.py:116-117,141-142 as pinv sees them, svd.py:27-45), the rest taken in descending order: P = sum_j e_j e_j^T / lambda_j
 int cur_gram_pinv(pmf_ctx* c, const float* G, int64_t ldg, int q, int qp, int inner, bool trans, const std::vector<double>& d,
                   std::vector<double>& P) {
-  const int nj = q + (q & 1);
   DevTemps tmp;
-  double *A = nullptr, *A2 = nullptr, *QT = nullptr, *evals = nullptr, *dd = nullptr;
-  int* info = nullptr;
-  PMFCHK(talloc(c, tmp, &A, (size_t)qp * qp));
-  PMFCHK(talloc(c, tmp, &A2, (size_t)qp * qp));
-  PMFCHK(talloc(c, tmp, &QT, (size_t)qp * qp));
-  PMFCHK(talloc(c, tmp, &evals, (size_t)qp));
+  double *QT = nullptr, *dd = nullptr;
   PMFCHK(talloc(c, tmp, &dd, (size_t)qp));
-  PMFCHK(talloc(c, tmp, &info, 2));
   HIPCHK(c, hipMemcpyAsync(dd, d.data(), (size_t)q * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  PMFCHK(gram_f64(c, G, ldg, qp, inner, trans, A, tmp));
-  hipLaunchKernelGGL(k_cur_scale_sym, dim3((unsigned)((q * q + 255) / 256)), dim3(256), 0, c->stream, A, qp, q, (const double*)dd);
-  HIPCHK(c, hipGetLastError());
-  PMFCHK(jacobi_eigh_dev(c, A, A2, QT, qp, nj, evals, info));
-  std::vector<double> ev((size_t)nj), E((size_t)nj * qp);
-  HIPCHK(c, hipMemcpyAsync(ev.data(), evals, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  std::vector<double> ev;
+  std::vector<int> ord;
+  PMFCHK(gram_eigh(c, G, ldg, q, qp, inner, trans, dd, tmp, ev, ord, &QT));
+  std::vector<double> E(ev.size() * qp);
   HIPCHK(c, hipMemcpyAsync(E.data(), QT, E.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
-  std::vector<int> ord;
-  for (int j = 0; j < nj; ++j)
-    if (ev[(size_t)j] > 1e-8) ord.push_back(j);
-  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return ev[(size_t)a] > ev[(size_t)b]; });
   P.assign((size_t)q * q, 0.0);
   for (int j : ord) {
     const double* e = E.data() + (size_t)j * qp;
@@ -115,7 +82,7 @@ int cur_indices(pmf_ctx* c, const int32_t* id, const int32_t* cnt, int n, int64_
 }
 
 // cur.py:99-120 on the resident V: C = data[:, cid] diag(sqrt(ccnt)), R = diag(sqrt(rcnt)) data[rid, :],
-// U = pinv(C) data pinv(R) = (C^T C)^+ (dc o (Cg^T data Rg^T) o dr) (R R^T)^+ (pmf_cur.h).  The data are read once by k_cross_f64:
+// U = pinv(C) data pinv(R) = (C^T C)^+ (dc o (Cg^T data Rg^T) o dr) (R R^T)^+ (pmf_cur.h).  The data are read once by k_prod_f64:
 // rows <= cols: T [mp][rp] = V Rg^T, then M = Cg^T T; otherwise T' [cp][np] = Cg^T V, then M = T' Rg^T (float64 MFMA, dgemm64).
 // The c x r sized rest runs on the host in float64 in a fixed order.  Leaves W = C U and H = R, so that pmf_frobenius is
 // ||data - C U R|| (svd.py:92-107).
@@ -152,10 +119,10 @@ int cur_compute(pmf_ctx* c, const int32_t* rid, const int32_t* rcnt, int nr, con
                        trans ? side : (double*)nullptr);
     HIPCHK(c, hipGetLastError());
     if (trans) {
-      PMFCHK(cross_f64(c, true, c->dCurCg, cp, cp / 64, c->dV, np, np / 64, (int)mp, T, tmp));
+      PMFCHK(prod_f64(c, true, false, c->dCurCg, cp, cp / 64, c->dV, np, np / 64, (int)mp, T, np, SITE_CUR, tmp));
       PMFCHK(dgemm64(c, T, np, side, np, np, dM, rp, cp, rp, true));
     } else {
-      PMFCHK(cross_f64(c, false, c->dV, np, (int)(mp / 64), c->dCurRg, np, rp / 64, np, T, tmp));
+      PMFCHK(prod_f64(c, false, false, c->dV, np, (int)(mp / 64), c->dCurRg, np, rp / 64, np, T, rp, SITE_CUR, tmp));
       PMFCHK(dgemm64(c, side, mp, T, rp, (int)mp, dM, rp, cp, rp, false));
     }
     HIPCHK(c, hipMemcpyAsync(M.data(), dM, M.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));

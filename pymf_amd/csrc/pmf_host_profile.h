@@ -34,7 +34,7 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
   } else if (c->algo == PMF_ALGO_PCA) {
     st.site = SITE_SVD;
     const bool left = c->m > c->n;
-    st.name = left ? "k_gram_f64<true>" : "k_gram_f64<false>";
+    st.name = left ? "k_prod_f64<true,sym>" : "k_prod_f64<false,sym>";
     const double q = left ? n : m;
     st.flops = 2.0 * m * n * q;                                   // the whole Gram matrix ...
     st.exec_flops = m * n * (q + 64.0);                           // ... of which the upper block triangle is formed
@@ -42,7 +42,7 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
   } else if (c->algo == PMF_ALGO_CUR) {
     st.site = SITE_CUR;                                           // (nr = nc = the context's k assumed: the call may pass fewer)
     const bool trans = c->m > c->n;
-    st.name = trans ? "k_cross_f64<true>" : "k_cross_f64<false>";
+    st.name = trans ? "k_prod_f64<true,full>" : "k_prod_f64<false,full>";
     st.flops = st.exec_flops = 2.0 * m * n * k;                   // T = V Rg^T or T' = Cg^T V
     const double kp = (double)round_up(c->k, 64);                // V once and the gathered operand once: Rg [kp][np] or Cg [mp][kp]
     st.bytes = 4.0 * (double)c->mp * (double)c->np + 4.0 * kp * (trans ? (double)c->mp : (double)c->np);

@@ -12,24 +12,61 @@ void svd_chunks(int inner, int ntiles, int* nchunks, int* chunk_len) {
   *nchunks = (inner + *chunk_len - 1) / *chunk_len;
 }
 
-// A [qp][qp] float64 = X X^T (X [qp][inner]) or X^T X (trans: X [inner][qp]) of the float32 X with leading dimension ldx, zero
-// padded; qp and inner are multiples of 64
-int gram_f64(pmf_ctx* c, const float* X, int64_t ldx, int qp, int inner, bool trans, double* A, DevTemps& tmp) {
-  const int T = qp / PMF_SVD_TILE, ntiles = T * (T + 1) / 2;
+// O [.][ldo] float64 = A B^T (A [TA * 64][inner], B [TB * 64][inner]) or A^T B (trans: A [inner][TA * 64], B [inner][TB * 64]) of the
+// float32 A, B, zero padded; inner is a multiple of 64.  sym (A == B, TA == TB): the tiles of the upper block triangle only.  The
+// product launch is timed as the profiled site `site`.
+int prod_f64(pmf_ctx* c, bool trans, bool sym, const float* A, int64_t lda, int TA, const float* B, int64_t ldb, int TB, int inner,
+             double* O, int64_t ldo, int site, DevTemps& tmp) {
+  const int ntiles = sym ? TB * (TB + 1) / 2 : TA * TB;
   int nch = 1, cl = inner;
   svd_chunks(inner, ntiles, &nch, &cl);
   double* slab = nullptr;
   PMFCHK(talloc(c, tmp, &slab, (size_t)nch * ntiles * PMF_SVD_TILE * PMF_SVD_TILE));
-  const dim3 grid((unsigned)ntiles, (unsigned)nch);
-  stat_begin(c, SITE_SVD);
-  if (trans) hipLaunchKernelGGL(k_gram_f64<true>, grid, dim3(256), 0, c->stream, X, ldx, inner, cl, T, slab);
-  else hipLaunchKernelGGL(k_gram_f64<false>, grid, dim3(256), 0, c->stream, X, ldx, inner, cl, T, slab);
-  stat_end(c, SITE_SVD);
+  const auto prod = trans ? (sym ? k_prod_f64<true, true> : k_prod_f64<true, false>) : (sym ? k_prod_f64<false, true> : k_prod_f64<false, false>);
+  stat_begin(c, site);
+  hipLaunchKernelGGL(prod, dim3((unsigned)ntiles, (unsigned)nch), dim3(256), 0, c->stream, A, lda, B, ldb, inner, cl, TB, slab);
+  stat_end(c, site);
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_gram_reduce_f64, dim3((unsigned)ntiles * 64u), dim3(1024), 0, c->stream, (const double*)slab, nch, ntiles, T, A, (int64_t)qp);
+  hipLaunchKernelGGL(sym ? k_prod_reduce_f64<true> : k_prod_reduce_f64<false>, dim3((unsigned)ntiles * 64u), dim3(1024), 0, c->stream,
+                     (const double*)slab, nch, ntiles, TB, O, ldo);
   HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+// A [qp][qp] float64 = X X^T (X [qp][inner]) or X^T X (trans: X [inner][qp]) of the float32 X with leading dimension ldx, zero
+// padded; qp and inner are multiples of 64
+int gram_f64(pmf_ctx* c, const float* X, int64_t ldx, int qp, int inner, bool trans, double* A, DevTemps& tmp) {
+  const int T = qp / PMF_SVD_TILE;
+  PMFCHK(prod_f64(c, trans, true, X, ldx, T, X, ldx, T, inner, A, (int64_t)qp, SITE_SVD, tmp));
   hipLaunchKernelGGL(k_mirror_upper_f64, dim3((unsigned)(((int64_t)qp * qp + 255) / 256)), dim3(256), 0, c->stream, A, qp);
   HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+// The eigenpairs of the q x q Gram matrix of the float32 G (gram_f64's operand), scaled to diag(d) . diag(d) when d (q values on
+// the device) is given: float64 Gram matrix, float64 Jacobi.  ev = the q + (q & 1) eigenvalues (host), ord = the indices of those
+// > 1e-8 (svd.py:116-117,141-142) in descending order, QT [.][qp] = the eigenvectors by rows (device, in tmp).  Synchronises.
+int gram_eigh(pmf_ctx* c, const float* G, int64_t ldg, int q, int qp, int inner, bool trans, const double* d, DevTemps& tmp,
+              std::vector<double>& ev, std::vector<int>& ord, double** QT) {
+  const int nj = q + (q & 1);
+  double *A = nullptr, *A2 = nullptr, *evals = nullptr;
+  int* info = nullptr;
+  PMFCHK(talloc(c, tmp, &A, (size_t)qp * qp));
+  PMFCHK(talloc(c, tmp, &A2, (size_t)qp * qp));
+  PMFCHK(talloc(c, tmp, QT, (size_t)qp * qp));
+  PMFCHK(talloc(c, tmp, &evals, (size_t)qp));
+  PMFCHK(talloc(c, tmp, &info, 2));
+  PMFCHK(gram_f64(c, G, ldg, qp, inner, trans, A, tmp));
+  if (d) hipLaunchKernelGGL(k_cur_scale_sym, dim3((unsigned)((q * q + 255) / 256)), dim3(256), 0, c->stream, A, qp, q, d);
+  HIPCHK(c, hipGetLastError());
+  PMFCHK(jacobi_eigh_dev(c, A, A2, *QT, qp, nj, evals, info));
+  ev.resize((size_t)nj);
+  HIPCHK(c, hipMemcpyAsync(ev.data(), evals, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  ord.clear();
+  for (int j = 0; j < nj; ++j)
+    if (ev[(size_t)j] > 1e-8) ord.push_back(j);
+  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return ev[(size_t)a] > ev[(size_t)b]; });
   return PMF_OK;
 }
 
@@ -52,28 +89,16 @@ int svd_dense(pmf_ctx* c) {
   if (c->svd_valid) return PMF_OK;
   const bool left = c->m > c->n;
   const int q = (int)(left ? c->n : c->m), qp = left ? c->np : (int)c->mp, KP = c->KP;
-  const int nj = q + (q & 1);
   PMFCHK(svd_alloc(c));
   DevTemps tmp;
-  double *A = nullptr, *A2 = nullptr, *QT = nullptr, *evals = nullptr;
+  double* QT = nullptr;
   float* B = nullptr;
-  int *info = nullptr, *order = nullptr;
-  PMFCHK(talloc(c, tmp, &A, (size_t)qp * qp));
-  PMFCHK(talloc(c, tmp, &A2, (size_t)qp * qp));
-  PMFCHK(talloc(c, tmp, &QT, (size_t)qp * qp));
-  PMFCHK(talloc(c, tmp, &evals, (size_t)qp));
-  PMFCHK(talloc(c, tmp, &info, 2));
+  int* order = nullptr;
   PMFCHK(talloc(c, tmp, &order, (size_t)KP));
   if (left) PMFCHK(talloc(c, tmp, &B, (size_t)KP * qp));
-  PMFCHK(gram_f64(c, c->dV, (int64_t)c->np, qp, left ? (int)c->mp : c->np, left, A, tmp));
-  PMFCHK(jacobi_eigh_dev(c, A, A2, QT, qp, nj, evals, info));
-  std::vector<double> ev((size_t)nj);
-  HIPCHK(c, hipMemcpyAsync(ev.data(), evals, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<double> ev;
   std::vector<int> ord;
-  for (int j = 0; j < nj; ++j)
-    if (ev[(size_t)j] > 1e-8) ord.push_back(j);
-  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return ev[(size_t)a] > ev[(size_t)b]; });
+  PMFCHK(gram_eigh(c, c->dV, (int64_t)c->np, q, qp, left ? (int)c->mp : c->np, left, nullptr, tmp, ev, ord, &QT));
   const int r = (int)ord.size();
   if (r > KP) return fail(c, PMF_EINVAL, "SVD: the rank exceeds the context's base count");
   std::vector<double> sv((size_t)KP, 0.0);

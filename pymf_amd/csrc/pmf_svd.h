@@ -14,41 +14,52 @@ constexpr int PMF_SVD_MIN_CHUNK = 512;      // ... and at least this much of the
 constexpr int PMF_SVD_TARGET_WGS = 512;     // tiles x chunks aimed at
 constexpr int PMF_SVD_MAX_RANK = 2432;      // min(rows, cols): the Jacobi limit is 4096, the product paths carry 2432 bases
 
-// Partial tile of A = V V^T (TRANS = false: q = mp, inner dimension the np columns) or A = V^T V (TRANS = true: q = np, inner
-// dimension the mp rows) of V [mp][ldv] float32, zero padded.  grid = (tiles of the upper block triangle, chunks of the inner
-// dimension), 256 threads: wave w owns rows 16 w .. 16 w + 15 of the tile, four 16 x 16 accumulators (the four column blocks).
+// Tile t of a product's tile grid -> (block row, block column).  SYM: the upper block triangle of a T x T grid, row by row
+// (row <= column); otherwise the full grid with T tile columns.
+template <bool SYM>
+__device__ __forceinline__ int2 prod_tile(int t, int T) {
+  if constexpr (!SYM) return make_int2(t / T, t % T);
+  int ti = 0;
+  while (t >= T - ti) { t -= T - ti; ++ti; }
+  return make_int2(ti, ti + t);
+}
+
+// Partial 64 x 64 tile of a float64 product of two float32 operands, zero padded to whole tiles and widened on load:
+//   TRANS = false: O [ra][rb] = sum_k A[ra][k] B[rb][k];   TRANS = true: O [ra][rb] = sum_k A[k][ra] B[k][rb].
+// SYM = true is a Gram matrix (A == B, lda == ldb: V V^T or V^T V of SVD / PCA, Cg^T Cg and Rg Rg^T of CUR), of which the upper
+// block triangle is formed; SYM = false the cross product of CUR (T = V Rg^T or T' = Cg^T V) on the full TA x TB grid.
+// grid = (tiles in prod_tile's order, chunks of the inner dimension), 256 threads: wave w owns rows 16 w .. 16 w + 15 of the
+// tile, four 16 x 16 accumulators (the four column blocks).
 // Operand order of v_mfma_f64_16x16x4_f64 (pmf_inv.h: tile_dgemm): lane l supplies row / column l & 15 at k = l >> 4.
 //   TRANS = false: both operands are contiguous along k.  Lane (i, g) fetches the four consecutive values k0 + 4 g .. + 3 of its
 //     row with one 16-byte load and feeds value u to MFMA step u: step u sums k0 + 4 g + u over g -- the same set for both
 //     operands, and the order of k inside a sum is free.
 //   TRANS = true: the lanes of one MFMA row (equal g) read 16 adjacent columns of row k0 + 4 s + g.
-// slab [chunk][tile][64][64] float64: no atomics, the chunks are added in a fixed order by k_gram_reduce_f64.
+// slab [chunk][tile][64][64] float64: no atomics, the chunks are added in a fixed order by k_prod_reduce_f64.
 // chunk_len and inner are multiples of 64.
-template <bool TRANS>
-__global__ __launch_bounds__(256) void k_gram_f64(const float* __restrict__ V, int64_t ldv, int inner, int chunk_len, int T,
-                                                  double* __restrict__ slab) {
-  int t = (int)blockIdx.x, ti = 0;
-  while (t >= T - ti) { t -= T - ti; ++ti; }          // tile (ti, tj), ti <= tj
-  const int tj = ti + t;
+template <bool TRANS, bool SYM>
+__global__ __launch_bounds__(256) void k_prod_f64(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
+                                                  int inner, int chunk_len, int TB, double* __restrict__ slab) {
+  const int2 tl = prod_tile<SYM>((int)blockIdx.x, TB);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int i = lane & 15, g = lane >> 4;
   const int k0 = (int)blockIdx.y * chunk_len;
   const int k1 = k0 + chunk_len < inner ? k0 + chunk_len : inner;
-  const int ra = ti * PMF_SVD_TILE + wv * 16 + i;     // the A operand's row of the Gram matrix
-  const int rb = tj * PMF_SVD_TILE + i;               // the B operand's: rb + 16 j
+  const int ra = tl.x * PMF_SVD_TILE + wv * 16 + i;   // the A operand's row of the output
+  const int rb = tl.y * PMF_SVD_TILE + i;             // the B operand's: rb + 16 j
   f64x4 acc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc[j] = f64x4{0.0, 0.0, 0.0, 0.0};
   if constexpr (!TRANS) {
-    const float* ap = V + (int64_t)ra * ldv + 4 * g;
-    const float* bp = V + (int64_t)rb * ldv + 4 * g;
+    const float* ap = A + (int64_t)ra * lda + 4 * g;
+    const float* bp = B + (int64_t)rb * ldb + 4 * g;
     for (int k = k0; k < k1; k += 32) {
       f32x4 a[2], b[2][4];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         a[h] = *reinterpret_cast<const f32x4*>(ap + k + 16 * h);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) b[h][j] = *reinterpret_cast<const f32x4*>(bp + (int64_t)(16 * j) * ldv + k + 16 * h);
+        for (int j = 0; j < 4; ++j) b[h][j] = *reinterpret_cast<const f32x4*>(bp + (int64_t)(16 * j) * ldb + k + 16 * h);
       }
 #pragma unroll
       for (int h = 0; h < 2; ++h)
@@ -58,15 +69,15 @@ __global__ __launch_bounds__(256) void k_gram_f64(const float* __restrict__ V, i
           for (int j = 0; j < 4; ++j) acc[j] = mfma_f64((double)a[h][u], (double)b[h][j][u], acc[j]);
     }
   } else {
-    const float* ap = V + (int64_t)g * ldv + ra;
-    const float* bp = V + (int64_t)g * ldv + rb;
+    const float* ap = A + (int64_t)g * lda + ra;
+    const float* bp = B + (int64_t)g * ldb + rb;
     for (int k = k0; k < k1; k += 16) {
       float a[4], b[4][4];
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        a[s] = ap[(int64_t)(k + 4 * s) * ldv];
+        a[s] = ap[(int64_t)(k + 4 * s) * lda];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) b[s][j] = bp[(int64_t)(k + 4 * s) * ldv + 16 * j];
+        for (int j = 0; j < 4; ++j) b[s][j] = bp[(int64_t)(k + 4 * s) * ldb + 16 * j];
       }
 #pragma unroll
       for (int s = 0; s < 4; ++s)
@@ -82,29 +93,34 @@ __global__ __launch_bounds__(256) void k_gram_f64(const float* __restrict__ V, i
     for (int r = 0; r < 4; ++r) o[(wv * 16 + g + 4 * r) * PMF_SVD_TILE + 16 * j + i] = acc[j][r];
 }
 
-// A tile (ti, tj) = the sum of its nchunks partial tiles, in a fixed order: wave w adds chunks w, w + 16, ..., the 16 partial
-// sums are combined in wave order (as k_reduce_slabs_block).  grid = ntiles * 64 (64 elements per workgroup), 1024 threads.
-__global__ __launch_bounds__(1024) void k_gram_reduce_f64(const double* __restrict__ slab, int nchunks, int ntiles, int T,
-                                                          double* __restrict__ A, int64_t ld) {
-  __shared__ double part[16][64];
+// The sum of cnt partials p[0], p[stride], ... in a fixed order, one sum per lane of a 1024-thread workgroup: wave w adds
+// partials w, w + 16, ..., the 16 sums are combined in wave order through part (as k_reduce_slabs_block); every wave returns the sum.
+__device__ __forceinline__ double sum_partials16(const double* __restrict__ p, int64_t stride, int cnt, double (*part)[64]) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int tile = (int)blockIdx.x >> 6;
-  const int e = (((int)blockIdx.x & 63) << 6) + lane;       // element of the tile
-  const int64_t stride = (int64_t)ntiles * (PMF_SVD_TILE * PMF_SVD_TILE);
-  const double* p = slab + (int64_t)tile * (PMF_SVD_TILE * PMF_SVD_TILE) + e;
   double s = 0.0;
 #pragma unroll 4
-  for (int ch = wv; ch < nchunks; ch += 16) s += p[ch * stride];
+  for (int q = wv; q < cnt; q += 16) s += p[q * stride];
   part[wv][lane] = s;
   __syncthreads();
-  if (wv == 0) {
-    double tot = part[0][lane];
+  double tot = part[0][lane];
 #pragma unroll
-    for (int w = 1; w < 16; ++w) tot += part[w][lane];
-    int t = tile, ti = 0;
-    while (t >= T - ti) { t -= T - ti; ++ti; }
-    const int tj = ti + t;
-    A[(int64_t)(ti * PMF_SVD_TILE + (e >> 6)) * ld + tj * PMF_SVD_TILE + (e & 63)] = tot;
+  for (int w = 1; w < 16; ++w) tot += part[w][lane];
+  return tot;
+}
+
+// Tile (ta, tb) of O [.][ld] (prod_tile's order, as k_prod_f64) = the sum of its nchunks partial tiles.
+// grid = ntiles * 64 (64 elements per workgroup), 1024 threads.
+template <bool SYM>
+__global__ __launch_bounds__(1024) void k_prod_reduce_f64(const double* __restrict__ slab, int nchunks, int ntiles, int TB,
+                                                          double* __restrict__ O, int64_t ld) {
+  __shared__ double part[16][64];
+  const int tile = (int)blockIdx.x >> 6;
+  const int e = (((int)blockIdx.x & 63) << 6) + (threadIdx.x & 63);       // element of the tile
+  const double tot = sum_partials16(slab + (int64_t)tile * (PMF_SVD_TILE * PMF_SVD_TILE) + e,
+                                    (int64_t)ntiles * (PMF_SVD_TILE * PMF_SVD_TILE), nchunks, part);
+  if (threadIdx.x < 64) {
+    const int2 tl = prod_tile<SYM>(tile, TB);
+    O[((int64_t)tl.x * PMF_SVD_TILE + (e >> 6)) * ld + tl.y * PMF_SVD_TILE + (e & 63)] = tot;
   }
 }
 

@@ -4,7 +4,7 @@ CUR samples rows and columns of the data with probabilities proportional to thei
 data ~ C U R with C = data[:, cid] diag(sqrt(ccnt)), R = diag(sqrt(rcnt)) data[rid, :] and U = pinv(C) data pinv(R)
 (cur.py:84-138).  On the device the squared norms come from one read of the float32 data in float64 (k_cur_sqnorms), and
 U is computed as (C^T C)^+ (C^T data R^T) (R R^T)^+: the two small Gram matrices and the middle product, the one pass over
-the data, run in float64 on the float64 MFMA (k_gram_f64, k_cross_f64), the pseudo-inverses come from the float64 Jacobi
+the data, run in float64 on the float64 MFMA (one kernel, k_prod_f64, with two tile maps), the pseudo-inverses come from the float64 Jacobi
 solver with svd.py's 1e-8 cut on the eigenvalues.  U (= C), S (= the middle factor) and V (= R) come back as
 float64 arrays, as the reference returns them.
 

@@ -3,7 +3,7 @@
 The reference takes the SVD of the data through the eigen-decomposition of the Gram matrix on the short side
 (svd.py:110-158): data^T data for rows > cols (`_left_svd`), data data^T otherwise (`_right_svd`); eigenvalues <= 1e-8 are
 dropped, the rest sorted descending, S = sqrt, and the other side is projected (U = data V^T S^-1 or V = S^-1 U^T data).
-On the device the Gram matrix of the float32 data is formed in float64 on the float64 MFMA (k_gram_f64), decomposed by the
+On the device the Gram matrix of the float32 data is formed in float64 on the float64 MFMA (k_prod_f64, the upper block triangle), decomposed by the
 float64 Jacobi solver, and the projected side is multiplied in float32.  U (rows x r), S (r x r diagonal)
 and V (r x cols) come back as float64 arrays, as the reference returns them; r is the number of eigenvalues kept.
 

@@ -1,9 +1,9 @@
 """The device cases of CUR and CMD (tests/test_gpu_cur.py) and what makes the comparison with the float64 oracle meaningful
-(tests/test_cur_cases.py, no GPU): the smallest shapes at which k_cur_sqnorms, k_cur_gather, k_cross_f64 and the paths
+(tests/test_cur_cases.py, no GPU): the smallest shapes at which k_cur_sqnorms, k_cur_gather, k_prod_f64 (full tile grid) and the paths
 behind them can go wrong.
 
 "Low rank" data are rand(m, 12) rand(12, n) + 0.05 rand(m, n), "uniform" data plain rand(m, n), both float32.  Every case runs
-as CUR and, with the same seed, as CMD.  k_cross_f64 cuts the inner dimension as k_gram_f64 does (svd_cases.chunks): 300
+as CUR and, with the same seed, as CMD.  The cross product cuts the inner dimension as the Gram matrix does (one kernel, k_prod_f64: svd_cases.chunks): 300
 columns (padded to 320) are one chunk, 2 100 (padded to 2 112) four chunks of 576 with a ragged tail of 384.  With 70 draws
 from 130 rows a repeated index is as good as certain (tests/test_cur_cases.py asserts that the seeds at hand have them), so
 CUR's Gram matrices there are singular -- a null eigenvalue must be dropped -- and CMD's counts exceed 1.

@@ -1,5 +1,5 @@
 """The device cases of SVD and PCA (tests/test_gpu_svd.py) and what makes the comparison with the float64 oracle meaningful
-(tests/test_svd_cases.py, no GPU): the smallest shapes at which k_gram_f64 and the paths behind it can go wrong.
+(tests/test_svd_cases.py, no GPU): the smallest shapes at which k_prod_f64 (Gram tile map) and the paths behind it can go wrong.
 
 Data are U0 diag(s) V0^T with random orthonormal U0, V0 and a prescribed geometric spectrum, rounded to float32, so that by
 construction every kept eigenvalue of the Gram matrix is far above svd.py's 1e-8 cut, every dropped one far below it, and
@@ -7,7 +7,7 @@ adjacent singular values are at least 5 % apart (well-conditioned vectors: only 
 the kept eigenvalues within 1e-4 of the largest, at most 94 singular values fit: the two-tile shapes (130 rows or columns)
 have rank 90.
 
-k_gram_f64 cuts the inner dimension into chunks of at least PMF_SVD_MIN_CHUNK = 512 (a multiple of 64): 300 columns (padded
+k_prod_f64 cuts the inner dimension into chunks of at least PMF_SVD_MIN_CHUNK = 512 (a multiple of 64): 300 columns (padded
 to 320) are one chunk, 2 100 (padded to 2 112) four chunks of 576 with a ragged tail of 384.
 """
 import json
@@ -83,7 +83,7 @@ def pca_data(name):
 
 
 def chunks(inner_padded, ntiles):
-    """(chunks, chunk length) of k_gram_f64 for a padded inner dimension: svd_chunks of pmf_host_svd.h."""
+    """(chunks, chunk length) of k_prod_f64 for a padded inner dimension: svd_chunks of pmf_host_svd.h."""
     nch = max(1, min(TARGET_WGS // ntiles, inner_padded // MIN_CHUNK))
     cl = -(-(-(-inner_padded // nch)) // 64) * 64
     return -(-inner_padded // cl), cl

@@ -5,7 +5,7 @@ order, S = sqrt, the other side projected (svd.py:110-158); PCA centres, takes t
 (pca.py:73-108).  tests/test_svd_oracle_golden.py holds it to goldens made by the real reference.
 
 The twin (f32=True) models the only float32 roundings of the device path: the data are rounded to float32 (the upload), the
-Gram matrix and its eigenpairs stay float64 (k_gram_f64, Jacobi), and the projected side is a float32 product of float32
+Gram matrix and its eigenpairs stay float64 (k_prod_f64, Jacobi), and the projected side is a float32 product of float32
 operands (U = data (v_i / s_i), or V = (u_i / s_i)^T data), as are PCA's H = W^T data and its float32 W.  The deviation between
 oracle and twin is what the device tolerances are derived from (tests/svd_cases.py).
 """

@@ -25,7 +25,7 @@ def test_constants_match_the_library():
 
 
 def test_shapes_cover_the_paths():
-    """k_cross_f64 shares svd_chunks with k_gram_f64: one chunk, four chunks with a ragged tail, two tiles per output side."""
+    """The cross product and the Gram matrix are one kernel, k_prod_f64, and share svd_chunks: one chunk, four chunks with a ragged tail, two tiles per output side."""
     assert sc.chunks(320, 1) == (1, 320)                       # 29 x 300: T = V Rg^T, one tile, one chunk
     assert sc.chunks(2112, 1) == (4, 576)                      # 29 x 2100
     assert sc.chunks(2112, 3 * 2) == (4, 576)                  # 130 x 2100 with 70 rows: 3 x 2 tiles, the last chunk 384 long

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """CUR at 64 x 1 048 576 with 64 sampled rows and columns on one MI355X: the two calls of a factorize() -- pmf_cur_sqnorms
-(one read of V by k_cur_sqnorms, its fixed-order reduce, m + n doubles to the host) and pmf_cur_compute (gather, k_cross_f64,
+(one read of V by k_cur_sqnorms, its fixed-order reduce, m + n doubles to the host) and pmf_cur_compute (gather, the cross product k_prod_f64<false,full>,
 the small products, two Gram matrices and Jacobi solves, W = C U and H = R) --, a few timed values each behind a warm-up call,
-median and spread; the time of k_cross_f64 (HIP events around every launch, in calls of their own, not the timed ones) with its
-achieved bytes and flops per second, beside its yardstick k_gram_f64<false> on the same data in the same process (a PCA
-context: it moves the same bytes and flops).  The time of k_cur_sqnorms alone is not taken here (one profiled site per
+median and spread; the time of the cross product (HIP events around every launch, in calls of their own, not the timed ones) with its
+achieved bytes and flops per second, beside its yardstick, the same kernel as Gram matrix (k_prod_f64<false,sym>) on the same data in the same process (a PCA
+context: it moves the same bytes and flops).  The JSON keys keep the kernels' earlier names, k_cross_f64 and k_gram_f64, so
+that old and new result files compare.  The time of k_cur_sqnorms alone is not taken here (one profiled site per
 context): its call is to be read against k_sivm_pass<l2> at this shape (64 us, profiles/sivm_bench.json), which also reads V
 once.  Writes profiles/cur_bench.json (or the path given as the first argument)."""
 import json
