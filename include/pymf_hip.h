@@ -41,6 +41,7 @@
  *   pmf_svd_decompose / pmf_svd_get  SVD.factorize, U / S / V  pymf/svd.py:110-158 (algo 12; PCA: pymf/pca.py)
  *   pmf_cur_sqnorms       CUR.sample_probability       pymf/cur.py:84-97 (algo 14)
  *   pmf_cur_compute / pmf_cur_get  CUR.computeUCR, C / U / R  pymf/cur.py:99-120 (CMD: pymf/cmd.py)
+ *   pmf_greedy_select     self.select of GREEDY        pymf/greedy.py:105-158 (algo 15; GREEDYCUR.sample: pymf/greedycur.py:62-68)
  *
  * Every function returns PMF_OK (0) or a negative status and never throws;
  * pmf_last_error() gives a human-readable message for the last failure.
@@ -69,6 +70,7 @@ enum {
 enum { PMF_ALGO_NMF = 0, PMF_ALGO_NMFALS = 1, PMF_ALGO_SNMF = 2, PMF_ALGO_BNMF = 3, PMF_ALGO_RNMF = 4, PMF_ALGO_CNMF = 5,
        PMF_ALGO_KMEANS = 6, PMF_ALGO_CMEANS = 8, PMF_ALGO_SIVM = 10, PMF_ALGO_AA = 11, PMF_ALGO_PCA = 12 };   /* 7 and 9 are not assigned: pmf_ctx_create refuses them */
 enum { PMF_ALGO_CUR = 14 };   /* CUR / CMD; 13 is not assigned and refused as well */
+enum { PMF_ALGO_GREEDY = 15 };   /* GREEDY (and, through pmf_greedy_select on a CUR context, GREEDYCUR) */
 
 /* pmf_factorize flags (the reference's factorize() keyword arguments, nmf.py:141-142) */
 enum { PMF_COMPUTE_W = 1u, PMF_COMPUTE_H = 2u, PMF_COMPUTE_ERR = 4u };
@@ -235,7 +237,7 @@ int pmf_cluster_set_assigned(pmf_ctx* ctx, const int32_t* assigned);
  *   pmf_factorize    update_w, update_h, ||V - W H|| under the PMF_COMPUTE_* flags; the class always passes niter = 1
  *   pmf_frobenius    the direct residual
  * pmf_sivm_get_select: the num_bases selected column indices of the last pmf_update_w in selection order; under 'origin' the
- * first is -1, which W treats as a Python index (the LAST data column, sivm.py:198). */
+ * first is -1, which W treats as a Python index (the LAST data column, sivm.py:198).  GREEDY contexts (algo 15) answer it too. */
 int pmf_sivm_get_select(pmf_ctx* ctx, int32_t* select);
 
 /* AA (algo 11; pymf/aa.py, archetypal analysis: column i of W is the projection of (data pinv(H))[:, i] onto the convex hull of
@@ -290,6 +292,25 @@ int pmf_svd_get(pmf_ctx* ctx, double* U, double* S, double* V);
 int pmf_cur_sqnorms(pmf_ctx* ctx, double* row_sq, double* col_sq);
 int pmf_cur_compute(pmf_ctx* ctx, const int32_t* rid, const int32_t* rcnt, int32_t nr, const int32_t* cid, const int32_t* ccnt, int32_t nc);
 int pmf_cur_get(pmf_ctx* ctx, double* C, double* U, double* R);
+
+/* GREEDY (algo 15; pymf/greedy.py for dense data, Civril and Magdon-Ismail: W = the num_bases data columns that best reproduce
+ * the leading singular subspace, chosen one after the other; H = pinv(W) data).  Dense resident data, one rank, num_bases <= 64,
+ * min(rows, cols) <= 2432 -- PMF_EINVAL otherwise.  The data are never rewritten: the reference's normalise-and-deflate loop is
+ * restated on the read-only data (pmf_greedy.h).
+ *   pmf_update_w     GREEDY.update_w (greedy.py:88-170): the eigenpairs of the float64 Gram matrix on the short side, then
+ *                    rows <= cols: num_bases rounds of one pass over V (k_greedy_pass) and one float64 step (k_greedy_step)
+ *                    enqueued back to back; rows > cols: all rounds in Gram space (k_greedy_gram).  Then W = V[:, select];
+ *                    needs V only.  pmf_sivm_get_select reads the selection.  Two runs give the same bits.
+ *   pmf_update_h     GREEDY.update_h (greedy.py:82-86): H = pinv(W) V, pinv(W) = (W^T W)^+ W^T in float64 with svd.py's cut
+ *                    (eigenvalues <= 1e-8 dropped), rounded once, the product on the fp32 MFMA; needs V and W.
+ *   pmf_factorize    NMF.factorize's loop; the steps repeat their result, so the convergence test stops it at the third iteration.
+ *   pmf_frobenius    the direct residual.
+ * A column whose residual against the columns chosen so far is at rounding level (norm^2 <= 512 unit roundoffs of its norm^2)
+ * scores 0; when every column does, the lowest index not yet chosen is taken.
+ * pmf_greedy_select: the selection alone -- nsel <= 64 indices in selection order -- among the columns of V (transposed = 0) or
+ * among its rows (transposed = 1: GREEDY on the transposed view, what GREEDYCUR's row selection is), on a GREEDY or a CUR / CMD
+ * context.  Both calls share the Gram matrix and its eigenpairs, formed once per V. */
+int pmf_greedy_select(pmf_ctx* ctx, int32_t transposed, int32_t nsel, int32_t* select);
 
 /* Device time (ms, HIP events on the library's stream) of the last pmf_factorize loop. */
 int pmf_last_loop_ms(pmf_ctx* ctx, double* ms);

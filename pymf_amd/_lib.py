@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("PMF_LIB") or os.path.join(_HERE, "csrc", "libpymf_hip
 PMF_OK, PMF_EINVAL, PMF_EHIP, PMF_ENCCL, PMF_ENOMEM, PMF_ESINGULAR, PMF_ENUMERIC = 0, -1, -2, -3, -4, -5, -6
 ALGO_NMF, ALGO_NMFALS, ALGO_SNMF, ALGO_BNMF, ALGO_RNMF, ALGO_CNMF, ALGO_KMEANS, ALGO_CMEANS, ALGO_SIVM, ALGO_AA, ALGO_PCA = 0, 1, 2, 3, 4, 5, 6, 8, 10, 11, 12   # (7, 9: not assigned)
 ALGO_CUR = 14   # (13: not assigned)
+ALGO_GREEDY = 15
 COMPUTE_W, COMPUTE_H, COMPUTE_ERR = 1, 2, 4
 STREAM_RESID = 8
 NCCL_ID_BYTES = 128
@@ -67,6 +68,7 @@ SYMBOLS = [
     ("pmf_cluster_get_assigned", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_cluster_set_assigned", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_sivm_get_select", _c.c_int, [_ctx, _c.c_void_p]),
+    ("pmf_greedy_select", _c.c_int, [_ctx, _c.c_int32, _c.c_int32, _c.c_void_p]),
     ("pmf_aa_get_beta", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_aa_rounds", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_svd_decompose", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
@@ -382,9 +384,16 @@ class Context(object):
         self._chk(self._lib.pmf_cluster_set_assigned(self._h, a.ctypes.data))
 
     def get_select(self):
-        """SIVM: the selected column indices of the last update_w, in selection order (pmf_sivm_get_select)."""
+        """SIVM, GREEDY: the selected column indices of the last update_w, in selection order (pmf_sivm_get_select)."""
         out = np.empty(self.k, dtype=np.int32)
         self._chk(self._lib.pmf_sivm_get_select(self._h, out.ctypes.data))
+        return out
+
+    def greedy_select(self, nsel, transposed=False):
+        """GREEDY / GREEDYCUR: `nsel` indices in selection order among the columns of the data, or (transposed) among its rows
+        (pmf_greedy_select)."""
+        out = np.empty(int(nsel), dtype=np.int32)
+        self._chk(self._lib.pmf_greedy_select(self._h, 1 if transposed else 0, int(nsel), out.ctypes.data))
         return out
 
     def get_beta(self):

@@ -40,6 +40,7 @@
 #include "pmf_aa.h"
 #include "pmf_svd.h"
 #include "pmf_cur.h"
+#include "pmf_greedy.h"
 
 // the internal host code, by concern (each header: one anonymous-namespace block; the order is the dependency order)
 #include "pmf_host_ctx.h"
@@ -58,6 +59,7 @@
 #include "pmf_host_aa.h"
 #include "pmf_host_svd.h"
 #include "pmf_host_cur.h"
+#include "pmf_host_greedy.h"
 #include "pmf_host_factorize.h"
 
 // =============================================================================================
@@ -84,8 +86,8 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                    int32_t rank, int32_t nranks, const void* nccl_id) {
   if (!out) return fail(nullptr, PMF_EINVAL, "out is NULL");
   *out = nullptr;
-  if (algo < 0 || algo > 14 || algo == 7 || algo == 9 || algo == 13)
-    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans), 8 (Cmeans), 10 (SIVM), 11 (AA), 12 (PCA / SVD) or 14 (CUR / CMD)");
+  if (algo < 0 || algo > 15 || algo == 7 || algo == 9 || algo == 13)
+    return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans), 8 (Cmeans), 10 (SIVM), 11 (AA), 12 (PCA / SVD), 14 (CUR / CMD) or 15 (GREEDY)");
   if (m_local < 1 || n < 1 || k < 1) return fail(nullptr, PMF_EINVAL, "m, n, k must be >= 1");
   if (algo == PMF_ALGO_CNMF) {  // C = V^T V is n x n float64 (128 MiB at the limit); the k x k factors on one float64 MFMA tile row
     if (n > 4096) return fail(nullptr, PMF_EINVAL, "CNMF: n (samples) > 4096 is not supported by this build");
@@ -119,6 +121,12 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
   if (algo == PMF_ALGO_CUR) {   // the sampled rows and columns are two 64-wide tiles of k_prod_f64 and one 128-wide block of W and H
     if (k > PMF_CUR_MAX_RANK) return fail(nullptr, PMF_EINVAL, "CUR / CMD: more than 128 sampled rows or columns are not supported by this build");
     if (nranks > 1) return fail(nullptr, PMF_EINVAL, "CUR / CMD: one rank only in this build");
+  }
+  if (algo == PMF_ALGO_GREEDY) {   // the staged operand [B' | Q] of k_greedy_pass has 2 k - 1 <= 127 columns; the short side goes through the Jacobi solver
+    if (k > PMF_GREEDY_MAX_BASES) return fail(nullptr, PMF_EINVAL, "GREEDY: num_bases > 64 is not supported by this build");
+    if (std::min<int64_t>(m_local, n) > PMF_SVD_MAX_RANK)
+      return fail(nullptr, PMF_EINVAL, "GREEDY: min(rows, cols) > 2432 is not supported by this build");
+    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "GREEDY: one rank only in this build");
   }
   // The reference has no limit on num_bases (nmf.py:116-120); the generic kernels beyond 128 bases have been checked against
   // the float64 oracles at 1 500, 2 304 and 2 432 bases (tests/sweeps/bigk_limit_probe.py, tests/test_gpu_bigk.py); beyond 2 432 (19 blocks of 128)
@@ -240,6 +248,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
   if (algo == PMF_ALGO_AA) c->path = "aa_pricing";
   if (algo == PMF_ALGO_PCA) c->path = "svd_gram_f64";
   if (algo == PMF_ALGO_CUR) c->path = "cur_cross_f64";
+  if (algo == PMF_ALGO_GREEDY) c->path = "greedy_panels";
   choose_stat_site(c, false);
   *out = c;
   return PMF_OK;
@@ -481,6 +490,12 @@ int pmf_update_w(pmf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
   }
+  if (c && c->algo == PMF_ALGO_GREEDY) {               // (the selection reads the data alone: greedy.py:88-170)
+    PMFCHK(need(c, true, false, false));
+    PMFCHK(greedy_update_w(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMF_OK;
+  }
   if (c && c->algo == PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "CUR / CMD: no W step (pmf_cur_compute is the decomposition)");
   if (c && c->algo == PMF_ALGO_PCA) {                  // (the decomposition reads the data alone: pca.py:93-108)
     PMFCHK(need(c, true, false, false));
@@ -516,6 +531,12 @@ int pmf_update_h(pmf_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PMF_OK;
   }
+  if (c && c->algo == PMF_ALGO_GREEDY) {               // greedy.py:82-86
+    PMFCHK(need(c, true, true, false));
+    PMFCHK(greedy_update_h(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PMF_OK;
+  }
   if (c && c->algo == PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "CUR / CMD: no H step (pmf_cur_compute is the decomposition)");
   if (c && c->algo == PMF_ALGO_PCA) {                  // pca.py:90-91
     PMFCHK(need(c, true, true, false));
@@ -535,7 +556,7 @@ int pmf_frobenius(pmf_ctx* c, double* out) {
     PMFCHK(cnmf_ready(c));
     return cnmf_error(c, false, out);
   }
-  if (is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA || c->algo == PMF_ALGO_CUR) return frobenius_direct(c, out);
+  if (is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA || c->algo == PMF_ALGO_CUR || c->algo == PMF_ALGO_GREEDY) return frobenius_direct(c, out);
   if (c->algo == PMF_ALGO_PCA) return pca_error(c, out);
   PMFCHK(do_frobenius(c, out));
   return ipc_check(c);
@@ -545,7 +566,7 @@ int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, do
                   int32_t* iters_done, int32_t* converged_at) {
   const bool cw = flags & PMF_COMPUTE_W, ch = flags & PMF_COMPUTE_H, ce = flags & PMF_COMPUTE_ERR;
   if (c && c->algo == PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "CUR / CMD: no iteration (pmf_cur_compute is the decomposition)");
-  if (c && (c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_PCA)) PMFCHK(need(c, true, !cw, !ch));   // (either step writes its factor from scratch)
+  if (c && (c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_PCA || c->algo == PMF_ALGO_GREEDY)) PMFCHK(need(c, true, !cw, !ch));   // (either step writes its factor from scratch)
   else if (c && c->algo == PMF_ALGO_AA) PMFCHK(need(c, true, !cw, cw || !ch));   // (the W step reads H, the H step W)
   else PMFCHK(need(c, true, true, true));
   if (niter < 0 || (ce && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
@@ -553,6 +574,7 @@ int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, do
   if (converged_at) *converged_at = -1;
   if (c->algo == PMF_ALGO_SIVM) { SivmLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
   if (c->algo == PMF_ALGO_PCA) { PcaLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
+  if (c->algo == PMF_ALGO_GREEDY) { GreedyLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
   if (c->algo == PMF_ALGO_AA) {
     if (c->v_csr) return fail(c, PMF_EINVAL, "AA: dense data only");
     AaLoopSteps s{cw, ch};
@@ -584,12 +606,19 @@ int pmf_cluster_get_assigned(pmf_ctx* c, int32_t* assigned) {
 
 int pmf_sivm_get_select(pmf_ctx* c, int32_t* select) {
   if (!c || !select) return fail(c, PMF_EINVAL, "pmf_sivm_get_select: bad arguments");
-  if (c->algo != PMF_ALGO_SIVM) return fail(c, PMF_EINVAL, "pmf_sivm_get_select: SIVM only");
+  if (c->algo != PMF_ALGO_SIVM && c->algo != PMF_ALGO_GREEDY) return fail(c, PMF_EINVAL, "pmf_sivm_get_select: SIVM and GREEDY only");
   if (!c->sv_have_select) return fail(c, PMF_EINVAL, "pmf_sivm_get_select: no selection yet (update_w has not run)");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(select, c->dSvSel, (size_t)c->k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return PMF_OK;
+}
+
+int pmf_greedy_select(pmf_ctx* c, int32_t transposed, int32_t nsel, int32_t* select) {
+  if (!c || !select) return fail(c, PMF_EINVAL, "pmf_greedy_select: bad arguments");
+  if (c->algo != PMF_ALGO_GREEDY && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_greedy_select: GREEDY and CUR / CMD contexts only");
+  PMFCHK(need(c, true, false, false));
+  return greedy_select_host(c, transposed != 0, nsel, select);
 }
 
 int pmf_aa_get_beta(pmf_ctx* c, double* beta) {
@@ -723,7 +752,7 @@ int pmf_rnmf_set_s_f32(pmf_ctx* c, const float* S) {
 int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (c) c->hd_synced = false;
   if (!c) return PMF_EINVAL;
-  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA || c->algo == PMF_ALGO_PCA || c->algo == PMF_ALGO_CUR)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
+  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA || c->algo == PMF_ALGO_PCA || c->algo == PMF_ALGO_CUR || c->algo == PMF_ALGO_GREEDY)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (!c->have_w || !c->have_h) return fail(c, PMF_EINVAL, "pmf_stream_begin: W and H must be set");
   if (max_tile_rows < 1) return fail(c, PMF_EINVAL, "pmf_stream_begin: max_tile_rows must be >= 1");

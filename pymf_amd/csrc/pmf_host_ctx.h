@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_AA, SITE_SVD, SITE_CUR };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY };
 
 struct KernelStat {
   std::string name = "none";
@@ -192,6 +192,14 @@ struct pmf_ctx {
   int cur_nr = 0, cur_nc = 0;
   std::vector<double> cur_dc, cur_dr, cur_U;
   bool cur_valid = false;       // they belong to the current V.  <- V
+  // GREEDY / GREEDYCUR (pmf_greedy.h): the float64 Gram matrix on the short side of V and the rows of its eigenvectors ([qp][qp]
+  // each), on the host the eigenvalues and the indices of those above svd.py's 1e-8 cut in descending order; pinv(W)^T [mp][KP]
+  // float32, the operand of H = pinv(W) data.  The selection itself is read through dSvSel / sv_have_select (SIVM's).
+  double *dGrG = nullptr, *dGrQT = nullptr;
+  float* dGrMT = nullptr;
+  std::vector<double> gr_ev;
+  std::vector<int> gr_ord;
+  bool gr_eig_valid = false;    // they belong to the current V.  <- V
   double lamb_w = 0.0, lamb_h = 0.0;   // BNMF penalty weights (bnmf.py:84-85,118-119)
   // streamed V (pmf_stream_*): row tiles pass through two device buffers, V is never resident
   float* dTile[2] = {nullptr, nullptr};
@@ -395,6 +403,7 @@ void v_replaced(pmf_ctx* c) {
   c->cl_sums_valid = c->cl_err_valid = c->cl_mu_valid = false;
   c->svd_valid = false;
   c->cur_valid = false;
+  c->gr_eig_valid = false;
 }
 void w_replaced(pmf_ctx* c, bool by_caller) {   // by_caller: uploaded or filled through the ABI (not the NNDSVD init, not a restored snapshot)
   c->have_w = true; c->ps_valid = c->num_valid = c->trace_ready = c->w_implicit = false;

@@ -46,6 +46,12 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.flops = st.exec_flops = 2.0 * m * n * k;                   // T = V Rg^T or T' = Cg^T V
     const double kp = (double)round_up(c->k, 64);                // V once and the gathered operand once: Rg [kp][np] or Cg [mp][kp]
     st.bytes = 4.0 * (double)c->mp * (double)c->np + 4.0 * kp * (trans ? (double)c->mp : (double)c->np);
+  } else if (c->algo == PMF_ALGO_GREEDY) {
+    st.site = SITE_GREEDY;                                        // (rows <= cols: the last round's pass, 2 k - 1 operand columns)
+    snprintf(buf, sizeof(buf), "k_greedy_pass<%d>", std::max(1, (2 * c->k - 1 + 15) / 16));
+    st.name = buf;
+    st.flops = st.exec_flops = 2.0 * m * n * (2.0 * k - 1.0);     // [B' | Q]^T V
+    st.bytes = 4.0 * m * (double)c->np + 9.0 * (double)c->np;    // V once; the norms and the flags of the chosen columns
   } else if (c->algo == PMF_ALGO_SNMF && gram) {
     st.site = SITE_MATERIALIZE;                   // the only m-sized kernel of a Gram-space loop: W = V M, once
     if (use_csr(c)) {
