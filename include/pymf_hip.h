@@ -38,6 +38,7 @@
  *   pmf_set/get_g_f64     self.G of CNMF               pymf/cnmf.py:95-100
  *   pmf_cluster_get/set_assigned  self.assigned of Kmeans  pymf/kmeans.py:77 (algo 6)
  *   pmf_sivm_get_select   self.select of SIVM          pymf/sivm.py:145-166,193 (algo 10)
+ *   pmf_sivm_select       SIVM_CUR.sample              pymf/sivm_cur.py:65-73 (algo 10 or 14)
  *   pmf_svd_decompose / pmf_svd_get  SVD.factorize, U / S / V  pymf/svd.py:110-158 (algo 12; PCA: pymf/pca.py)
  *   pmf_cur_sqnorms       CUR.sample_probability       pymf/cur.py:84-97 (algo 14)
  *   pmf_cur_compute / pmf_cur_get  CUR.computeUCR, C / U / R  pymf/cur.py:99-120 (CMD: pymf/cmd.py)
@@ -239,6 +240,19 @@ int pmf_cluster_set_assigned(pmf_ctx* ctx, const int32_t* assigned);
  * pmf_sivm_get_select: the num_bases selected column indices of the last pmf_update_w in selection order; under 'origin' the
  * first is -1, which W treats as a Python index (the LAST data column, sivm.py:198).  GREEDY contexts (algo 15) answer it too. */
 int pmf_sivm_get_select(pmf_ctx* ctx, int32_t* select);
+
+/* pmf_sivm_select: SIVM's selection alone (pymf/sivm_cur.py:65-73: what SIVM_CUR.sample asks of SIVM) on a SIVM or a CUR / CMD
+ * context -- nsel indices in selection order among the columns of V (transposed = 0) or among its rows (transposed = 1: SIVM on
+ * the transposed view), under metric 0 'l2', 1 'l1' or 2 'cosine' and init 0 'fastmap' or 1 'origin' (the first entry is then -1).
+ * path 0 chooses the kernel by shape: columns run k_sivm_pass on V while rows <= 16384 and otherwise the long-sample pass
+ * (k_sivm_rowdist, k_sivm_rowstep: pmf_sivm.h) on a transposed copy; rows run the long-sample pass on V itself, without a copy,
+ * while rows <= 16384 and otherwise k_sivm_pass on the transposed copy.  path 1 forces k_sivm_pass, path 2 the long-sample pass,
+ * each on a transposed copy where the layout needs one; PMF_EINVAL where the kernel's limit (samples of dimension <= 16384;
+ * at most 16384 candidates) does not allow it.  All rounds are enqueued back to back; state and partials are temporaries of
+ * the call: the context's own selection state, pmf_update_w and pmf_sivm_get_select are not touched.  Dense resident data, one
+ * rank, 1 <= nsel <= 64, min(rows, cols) <= 16384 -- PMF_EINVAL otherwise.  Two calls give the same bits.
+ * pmf_set_option "profile_sivm_rows" (0 default, 1) makes pmf_profile_enable time the rounds of the long-sample pass. */
+int pmf_sivm_select(pmf_ctx* ctx, int32_t transposed, int32_t nsel, int32_t metric, int32_t init, int32_t path, int32_t* select);
 
 /* AA (algo 11; pymf/aa.py, archetypal analysis: column i of W is the projection of (data pinv(H))[:, i] onto the convex hull of
  * the data columns, W = data beta^T with beta >= 0 and rows summing to 1; the H step is the one SIVM inherits).  Dense resident

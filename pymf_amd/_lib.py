@@ -69,6 +69,7 @@ SYMBOLS = [
     ("pmf_cluster_set_assigned", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_sivm_get_select", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_greedy_select", _c.c_int, [_ctx, _c.c_int32, _c.c_int32, _c.c_void_p]),
+    ("pmf_sivm_select", _c.c_int, [_ctx, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p]),
     ("pmf_aa_get_beta", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_aa_rounds", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_svd_decompose", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
@@ -394,6 +395,14 @@ class Context(object):
         (pmf_greedy_select)."""
         out = np.empty(int(nsel), dtype=np.int32)
         self._chk(self._lib.pmf_greedy_select(self._h, 1 if transposed else 0, int(nsel), out.ctypes.data))
+        return out
+
+    def sivm_select(self, nsel, transposed=False, metric=0, init=0, path=0):
+        """SIVM / SIVM_CUR: `nsel` indices in SIVM's selection order among the columns of the data, or (transposed) among its
+        rows; metric 0 l2, 1 l1, 2 cosine; init 0 fastmap, 1 origin (the first entry is then -1); path 0 by shape, 1 the
+        column-panel pass, 2 the long-sample pass (pmf_sivm_select)."""
+        out = np.empty(max(int(nsel), 0), dtype=np.int32)
+        self._chk(self._lib.pmf_sivm_select(self._h, 1 if transposed else 0, int(nsel), int(metric), int(init), int(path), out.ctypes.data))
         return out
 
     def get_beta(self):

@@ -621,6 +621,13 @@ int pmf_greedy_select(pmf_ctx* c, int32_t transposed, int32_t nsel, int32_t* sel
   return greedy_select_host(c, transposed != 0, nsel, select);
 }
 
+int pmf_sivm_select(pmf_ctx* c, int32_t transposed, int32_t nsel, int32_t metric, int32_t init, int32_t path, int32_t* select) {
+  if (!c || !select) return fail(c, PMF_EINVAL, "pmf_sivm_select: bad arguments");
+  if (c->algo != PMF_ALGO_SIVM && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_sivm_select: SIVM and CUR / CMD contexts only");
+  PMFCHK(need(c, true, false, false));
+  return sivm_select_host(c, transposed != 0, nsel, metric, init, path, select);
+}
+
 int pmf_aa_get_beta(pmf_ctx* c, double* beta) {
   if (!c || !beta) return fail(c, PMF_EINVAL, "pmf_aa_get_beta: bad arguments");
   if (c->algo != PMF_ALGO_AA) return fail(c, PMF_EINVAL, "pmf_aa_get_beta: AA only");
@@ -1258,6 +1265,13 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
       if (value != 0 && value != 1) return fail(c, PMF_EINVAL, "sivm_init: 0 (fastmap) or 1 (origin)");
       c->sv_init = (int)value;
     }
+    return PMF_OK;
+  }
+  if (std::strcmp(name, "profile_sivm_rows") == 0) {
+    if (c->algo != PMF_ALGO_SIVM && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "profile_sivm_rows: SIVM and CUR / CMD contexts only");
+    if (value != 0 && value != 1) return fail(c, PMF_EINVAL, "profile_sivm_rows: 0 or 1");
+    c->opt_profile_sivm_rows = (int)value;
+    choose_stat_site(c, false);
     return PMF_OK;
   }
   if (std::strcmp(name, "snmf_gram") == 0) {

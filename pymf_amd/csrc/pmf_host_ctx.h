@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_SIVM_ROWS, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY };
 
 struct KernelStat {
   std::string name = "none";
@@ -170,6 +170,7 @@ struct pmf_ctx {
   int sv_metric = 0;            // pmf_set_option("sivm_metric"): 0 l2, 1 l1, 2 cosine
   int sv_init = 0;              // pmf_set_option("sivm_init"): 0 fastmap, 1 origin
   bool sv_have_select = false;  // dSvSel holds the selection of a W step
+  int opt_profile_sivm_rows = 0;   // pmf_set_option("profile_sivm_rows"): pmf_profile_enable times the rounds of the long-sample pass (SITE_SIVM_ROWS)
   // AA (pmf_aa.h): W_hat, the points X and residuals R ([mp][KP]); the two partials arrays of the pricing pass ([2][wgs][KP]); per
   // base the corral's Gram matrix, data columns and weights by slot, the finished flag; unfinished bases per round; the
   // inverse's verdict (zero pivot, pivots above 1e-8), inv(H H^T), beta [k][n]

@@ -13,7 +13,12 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
   const int old_site = st.site;
   st.site = SITE_NONE; st.name = "none"; st.flops = st.bytes = st.exec_flops = 0.0;
   char buf[96];
-  if (c->algo == PMF_ALGO_KMEANS || c->algo == PMF_ALGO_CMEANS) {
+  if (c->opt_profile_sivm_rows && (c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_CUR)) {
+    st.site = SITE_SIVM_ROWS;                                     // one round of the long-sample pass; pmf_sivm_select restates the
+    st.name = "k_sivm_rowdist<l2>+k_sivm_rowstep";                // figures for the matrix, the side and the measure of the call
+    st.flops = st.exec_flops = 3.0 * m * n;
+    st.bytes = 4.0 * m * (double)c->np;
+  } else if (c->algo == PMF_ALGO_KMEANS || c->algo == PMF_ALGO_CMEANS) {
     st.site = SITE_CLUSTER;
     snprintf(buf, sizeof(buf), "k_cluster_pass<%d,%s>", c->NT, c->algo == PMF_ALGO_KMEANS ? "kmeans" : "cmeans");
     st.name = buf;

@@ -31,11 +31,12 @@ int sivm_alloc(pmf_ctx* c) {
   return PMF_OK;
 }
 
-int sivm_launch_pass(pmf_ctx* c, const SivmArgs& a) {
-  const dim3 grid((unsigned)c->sv_wgs), block(256);
-  const size_t smem = (size_t)c->m * sizeof(float);
+// one k_sivm_pass over the matrix that `a` describes (a.m rows staged in LDS)
+int sivm_launch_pass(pmf_ctx* c, const SivmArgs& a, int wgs, int metric) {
+  const dim3 grid((unsigned)wgs), block(256);
+  const size_t smem = (size_t)a.m * sizeof(float);
   stat_begin(c, SITE_SIVM);
-  switch (c->sv_metric) {
+  switch (metric) {
     case PMF_SIVM_L2: hipLaunchKernelGGL(k_sivm_pass<PMF_SIVM_L2>, grid, block, smem, c->stream, a); break;
     case PMF_SIVM_L1: hipLaunchKernelGGL(k_sivm_pass<PMF_SIVM_L1>, grid, block, smem, c->stream, a); break;
     default: hipLaunchKernelGGL(k_sivm_pass<PMF_SIVM_COSINE>, grid, block, smem, c->stream, a); break;
@@ -65,7 +66,7 @@ int sivm_update_w(pmf_ctx* c) {
     a.pscore_out = c->dSvPart + out * PMF_CL_MAX_WGS; a.pidx_out = c->dSvPartIdx + out * PMF_CL_MAX_WGS;
     a.nprev = nprev; a.use_fixed = use_fixed; a.sel_pos = sel_pos; a.take_maxd = take_maxd; a.plain = plain; a.l = l;
     ++pass;
-    return sivm_launch_pass(c, a);
+    return sivm_launch_pass(c, a, c->sv_wgs, c->sv_metric);
   };
   // sivm.py:145-166: three distance passes from column 0 ('fastmap'), or one from the origin
   const int nplain = origin ? 1 : 3;
@@ -83,6 +84,158 @@ int sivm_update_w(pmf_ctx* c) {
   HIPCHK(c, hipGetLastError());
   w_replaced(c, false);
   c->sv_have_select = true;
+  return PMF_OK;
+}
+
+// ---- pmf_sivm_select: the selection alone, among the columns of the resident V or among its rows (SIVM_CUR) --------------------
+// The rounds of update_w (sivm.py:145-201) as (plain, l, take_maxd, keep, sel_pos, last) per round: three plain rounds from
+// candidate 0 ('fastmap') or one from the origin, then round l measures against select[l - 1] and finds select[l].
+struct SivmRound { int plain, l, take_maxd, keep, sel_pos, last; };
+
+std::vector<SivmRound> sivm_rounds(int nsel, bool origin) {
+  std::vector<SivmRound> r;
+  const int nplain = origin ? 1 : 3;
+  for (int p = 0; p < nplain; ++p) r.push_back({1, 0, p == nplain - 1, origin ? 1 : 0, -1, 0});
+  for (int l = 1; l < nsel; ++l) r.push_back({0, l, 0, 0, l - 1, 0});
+  r.back().last = 1;
+  return r;
+}
+
+// k_sivm_pass on A [R rows][ld], candidates its C columns; state and partials are temporaries of the call
+int sivm_select_panels(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, int* dsel, DevTemps& tmp) {
+  const int npanels = (int)(ld / 64);
+  const int want = std::min(npanels, PMF_CL_MAX_WGS);
+  const int ppw = (npanels + want - 1) / want, wgs = (npanels + ppw - 1) / ppw;
+  double *state = nullptr, *part = nullptr, *scal = nullptr;
+  int* pidx = nullptr;
+  PMFCHK(talloc(c, tmp, &state, (size_t)3 * ld));
+  PMFCHK(talloc(c, tmp, &part, (size_t)2 * PMF_CL_MAX_WGS));
+  PMFCHK(talloc(c, tmp, &pidx, (size_t)2 * PMF_CL_MAX_WGS));
+  PMFCHK(talloc(c, tmp, &scal, 2));
+  HIPCHK(c, hipMemsetAsync(state, 0, (size_t)3 * ld * sizeof(double), c->stream));
+  SivmArgs a{};
+  a.V = A;
+  a.dij = state; a.dsum = state + ld; a.dsq = state + 2 * ld;
+  a.select = dsel; a.scal = scal;
+  a.np = ld; a.m = R; a.n = C;
+  a.npanels = npanels; a.panels_per_wg = ppw;
+  a.fixed_idx = origin ? -1 : 0;
+  const std::vector<SivmRound> rounds = sivm_rounds(nsel, origin);
+  for (size_t p = 0; p < rounds.size(); ++p) {         // as sivm_update_w: a round's argmax is taken in the next launch's prologue
+    const SivmRound& r = rounds[p];
+    const int out = (int)(p & 1), in = out ^ 1;
+    a.pscore_in = part + in * PMF_CL_MAX_WGS; a.pidx_in = pidx + in * PMF_CL_MAX_WGS;
+    a.pscore_out = part + out * PMF_CL_MAX_WGS; a.pidx_out = pidx + out * PMF_CL_MAX_WGS;
+    a.nprev = p == 0 ? 0 : wgs;
+    a.use_fixed = p == 0 || (origin && r.l == 1);
+    a.sel_pos = r.sel_pos; a.take_maxd = r.l == 1; a.plain = r.plain; a.l = r.l;
+    PMFCHK(sivm_launch_pass(c, a, wgs, metric));
+  }
+  const int last = (int)((rounds.size() - 1) & 1);
+  hipLaunchKernelGGL(k_sivm_close, dim3(1), dim3(256), 0, c->stream, (const double*)(part + last * PMF_CL_MAX_WGS),
+                     (const int*)(pidx + last * PMF_CL_MAX_WGS), wgs, C, nsel - 1, nsel == 1 ? 1 : 0, (origin && nsel == 1) ? 1 : 0, dsel, scal);
+  HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+template <int METRIC>
+void sivm_launch_rowdist(pmf_ctx* c, const SivmRowArgs& a) {
+  hipLaunchKernelGGL(k_sivm_rowdist<METRIC>, dim3((unsigned)a.slabs, (unsigned)((a.C + PMF_SIVM_ROWS_WG - 1) / PMF_SIVM_ROWS_WG)), dim3(256), 0,
+                     c->stream, a);
+}
+
+// the long-sample pass on A [C rows][ld], candidates its rows, R valid columns: two launches per round, enqueued back to back
+int sivm_select_rows(pmf_ctx* c, const float* A, int64_t ld, int C, int R, int nsel, int metric, bool origin, int* dsel, DevTemps& tmp) {
+  const int slabs = (R + PMF_SIVM_SLAB - 1) / PMF_SIVM_SLAB;
+  const int Cs = (int)round_up(C, PMF_SIVM_ROWS_WG);
+  const int64_t blk = (int64_t)slabs * Cs;
+  double *state = nullptr, *part = nullptr, *xpart = nullptr, *scal = nullptr;
+  int* cur = nullptr;
+  PMFCHK(talloc(c, tmp, &state, (size_t)3 * Cs));
+  PMFCHK(talloc(c, tmp, &part, (size_t)(metric == PMF_SIVM_COSINE ? 2 : 1) * blk));
+  PMFCHK(talloc(c, tmp, &xpart, (size_t)slabs));
+  PMFCHK(talloc(c, tmp, &scal, 2));
+  PMFCHK(talloc(c, tmp, &cur, 1));
+  HIPCHK(c, hipMemsetAsync(state, 0, (size_t)3 * Cs * sizeof(double), c->stream));
+  HIPCHK(c, hipMemsetAsync(cur, origin ? 0xff : 0, sizeof(int), c->stream));      // -1 or 0
+  SivmRowArgs d{};
+  d.A = A; d.ld = ld; d.cur = cur; d.part = part; d.xpart = xpart; d.C = C; d.R = R; d.Cs = Cs; d.slabs = slabs;
+  SivmRowStepArgs s{};
+  s.part = part; s.xpart = xpart; s.dij = state; s.dsum = state + Cs; s.dsq = state + 2 * Cs; s.cur = cur; s.select = dsel; s.scal = scal;
+  s.C = C; s.Cs = Cs; s.slabs = slabs; s.metric = metric;
+  s.tpr = 1;                                           // threads per row of the slab sum: all 256 busy while C is small
+  while (s.tpr < 64 && 2 * s.tpr * C <= 256 && s.tpr < slabs) s.tpr *= 2;
+  if (c->profile && c->stat.site == SITE_SIVM_ROWS) {
+    static const char* const names[3] = {"k_sivm_rowdist<l2>+k_sivm_rowstep", "k_sivm_rowdist<l1>+k_sivm_rowstep", "k_sivm_rowdist<cosine>+k_sivm_rowstep"};
+    c->stat.name = names[metric];
+    c->stat.flops = c->stat.exec_flops = (metric == PMF_SIVM_COSINE ? 4.0 : 3.0) * (double)C * (double)R;
+    // A once, x once per row block; the partials written and read; the state read and written
+    c->stat.bytes = 4.0 * (double)C * (double)R + 4.0 * (double)R * (double)(Cs / PMF_SIVM_ROWS_WG) +
+                    16.0 * (double)blk * (metric == PMF_SIVM_COSINE ? 2.0 : 1.0) + 48.0 * (double)C;
+  }
+  for (const SivmRound& r : sivm_rounds(nsel, origin)) {
+    stat_begin(c, SITE_SIVM_ROWS);
+    switch (metric) {
+      case PMF_SIVM_L2: sivm_launch_rowdist<PMF_SIVM_L2>(c, d); break;
+      case PMF_SIVM_L1: sivm_launch_rowdist<PMF_SIVM_L1>(c, d); break;
+      default: sivm_launch_rowdist<PMF_SIVM_COSINE>(c, d); break;
+    }
+    HIPCHK(c, hipGetLastError());
+    s.plain = r.plain; s.l = r.l; s.take_maxd = r.take_maxd; s.keep_cur = r.keep; s.sel_pos = r.sel_pos;
+    s.last_pos = r.last ? nsel - 1 : -1;
+    hipLaunchKernelGGL(k_sivm_rowstep, dim3(1), dim3(256), 0, c->stream, s);
+    stat_end(c, SITE_SIVM_ROWS);
+    HIPCHK(c, hipGetLastError());
+  }
+  return PMF_OK;
+}
+
+// nsel indices in selection order into dsel (device): among the columns of V, or (trans) among its rows.  path 0: by shape
+// (DESIGN.md 3.17); 1 / 2: k_sivm_pass / the long-sample pass forced, on a transposed copy where the layout needs one.
+// Synchronises at the end.
+bool sivm_rows_path(const pmf_ctx* c, bool trans, int path) {
+  return path == 0 ? (trans == (c->m <= PMF_SIVM_MAX_M)) : path == 2;
+}
+
+int sivm_select(pmf_ctx* c, bool trans, int nsel, int metric, bool origin, int path, int* dsel) {
+  const int64_t C = trans ? c->m : c->n, R = trans ? c->n : c->m;
+  const bool rows_path = sivm_rows_path(c, trans, path);
+  DevTemps tmp;
+  const float* A = c->dV;
+  int64_t ld = c->np;
+  if (rows_path != trans) {                            // the pass wants the other layout: the transposed view as a matrix of its own, [np][mp]
+    float* AT = nullptr;
+    PMFCHK(talloc(c, tmp, &AT, (size_t)c->np * c->mp));
+    hipLaunchKernelGGL(k_greedy_transpose, dim3((unsigned)(c->mp / 64), (unsigned)(c->np / 64)), dim3(256), 0, c->stream, (const float*)c->dV,
+                       (int64_t)c->np, AT, (int64_t)c->mp);
+    HIPCHK(c, hipGetLastError());
+    A = AT;
+    ld = c->mp;
+  }
+  if (rows_path) PMFCHK(sivm_select_rows(c, A, ld, (int)C, (int)R, nsel, metric, origin, dsel, tmp));
+  else PMFCHK(sivm_select_panels(c, A, ld, (int)R, (int)C, nsel, metric, origin, dsel, tmp));
+  HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
+  return PMF_OK;
+}
+
+// pmf_sivm_select: the arguments checked before anything is touched, the selection, read back
+int sivm_select_host(pmf_ctx* c, bool trans, int nsel, int metric, int init, int path, int32_t* select) {
+  if (c->v_csr || !c->dV) return fail(c, PMF_EINVAL, "pmf_sivm_select: dense resident data only");
+  if (multi_rank(c)) return fail(c, PMF_EINVAL, "pmf_sivm_select: one rank only in this build");
+  if (nsel < 1 || nsel > 64) return fail(c, PMF_EINVAL, "pmf_sivm_select: 1 <= nsel <= 64");
+  if (metric < 0 || metric > 2) return fail(c, PMF_EINVAL, "pmf_sivm_select: metric 0 (l2), 1 (l1) or 2 (cosine)");
+  if (init != 0 && init != 1) return fail(c, PMF_EINVAL, "pmf_sivm_select: init 0 (fastmap) or 1 (origin)");
+  if (path < 0 || path > 2) return fail(c, PMF_EINVAL, "pmf_sivm_select: path 0 (by shape), 1 (column panels) or 2 (long samples)");
+  if (std::min<int64_t>(c->m, c->n) > PMF_SIVM_MAX_M) return fail(c, PMF_EINVAL, "pmf_sivm_select: min(rows, cols) > 16384 is not supported by this build");
+  if (sivm_rows_path(c, trans, path) ? (trans ? c->m : c->n) > PMF_SIVM_ROW_MAX_C : (trans ? c->n : c->m) > PMF_SIVM_MAX_M)
+    return fail(c, PMF_EINVAL, path == 2 ? "pmf_sivm_select: the long-sample pass takes at most 16384 candidates"
+                                         : "pmf_sivm_select: the column-panel pass takes samples of dimension <= 16384");
+  DevTemps tmp;
+  int* dsel = nullptr;
+  PMFCHK(talloc(c, tmp, &dsel, 64));
+  PMFCHK(sivm_select(c, trans, nsel, metric, init == 1, path, dsel));
+  HIPCHK(c, hipMemcpyAsync(select, dsel, (size_t)nsel * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return PMF_OK;
 }
 

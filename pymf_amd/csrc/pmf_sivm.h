@@ -15,6 +15,8 @@
 // same way, the lowest index winning ties -- and works on that idx; workgroup 0 appends it to select[] and, behind the last
 // plain pass, writes maxd and a.  k_sivm_close does the last reduce, k_sivm_gather writes W = V[:, select] (a -1 entry is a
 // Python index there: the LAST data column).  Pad columns (c >= n) never win.  Two runs give the same bits.
+// The same selection among the ROWS of a row-major matrix, whose samples are too long for LDS, is the long-sample pass
+// further down (k_sivm_rowdist, k_sivm_rowstep): SIVM_CUR's row selection.
 #pragma once
 #include "pmf_dev.h"
 
@@ -215,6 +217,232 @@ __global__ __launch_bounds__(256) void k_sivm_gather(const float* __restrict__ V
     w = V[r * np + s];
   }
   W[i] = w;
+}
+
+// ---- the long-sample pass: SIVM among the ROWS of a row-major A [C][ld] (SIVM_CUR's row selection) ------------
+// The C <= 16 384 rows are the candidates, the R valid columns their dimension (64 x 1 048 576: 64 candidates of dimension one
+// million, which k_sivm_pass cannot stage).  One round is two launches:
+//   k_sivm_rowdist<METRIC>  grid (column slabs of PMF_SIVM_SLAB) x (blocks of PMF_SIVM_ROWS_WG rows): one read of A.  The slab's
+//                           piece of x = A[idx, :] (idx = *cur; -1: the origin, zeros) is staged in LDS once per workgroup; each of
+//                           the four waves owns PMF_SIVM_ROWS_WAVE rows and walks the slab 256 columns at a time, 16 bytes per lane,
+//                           coalesced along the row, one x read from LDS serving its eight rows.  Products and differences are fp32;
+//                           a fp32 running sum covers a lane's share of one slab of one row -- at most 32 terms (8 steps of 4
+//                           columns), the longest fp32 sum of this pass.  Everything above is float64 in a fixed order: the 64
+//                           lanes (xor butterfly), then the slabs (k_sivm_rowstep).  Partials [slab][row]: the distance sum (l2: of
+//                           squares, l1: of moduli; cosine: v.x and, behind it, |v|^2; |x|^2 per slab).  Rows >= C are never
+//                           written, columns >= R are masked to zero whatever the padding holds.
+//   k_sivm_rowstep          one workgroup: per row the slab partials in float64 (tpr threads of a row take every tpr-th slab in
+//                           ascending order, then an xor butterfly), dist (l2 sqrt, cosine 1 - v.x / (|v||x| + 1e-9), in float64),
+//                           the recurrence of k_sivm_pass and the argmax (sivm_better, sivm_wg_best); thread 0 leaves idx in *cur
+//                           for the next launch, appends to select[] and, behind the last plain pass, stores maxd and a.
+// No host read between rounds, no float atomics, two runs give the same bits.
+constexpr int PMF_SIVM_ROW_MAX_C = 16384;  // candidates of the long-sample pass (one workgroup does the score step)
+constexpr int PMF_SIVM_SLAB = 2048;        // columns per slab: 8 KiB of x in LDS, 8 steps of 256 columns
+constexpr int PMF_SIVM_ROWS_WAVE = 8;      // rows a wave carries through its slab
+constexpr int PMF_SIVM_ROWS_WG = 4 * PMF_SIVM_ROWS_WAVE;
+
+struct SivmRowArgs {
+  const float* A;          // [>= C rows][ld]
+  int64_t ld;
+  const int* cur;          // [1] the row this round measures against (-1: the origin)
+  double* part;            // [slabs][Cs]; cosine: a second block of the same size behind it
+  double* xpart;           // [slabs] |x|^2 (cosine)
+  int C, R, Cs, slabs;
+};
+
+// the sum of s over the 64 lanes in float64, a fixed order, the same bits in every lane
+__device__ __forceinline__ double sivm_wave_sum(double s) {
+#pragma unroll
+  for (int x = 1; x < 64; x <<= 1) s += __shfl_xor(s, x);
+  return s;
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_sivm_rowdist(const SivmRowArgs a) {
+  __shared__ __attribute__((aligned(16))) float xs[PMF_SIVM_SLAB];
+  __shared__ double xw[4];
+  constexpr int NR = PMF_SIVM_ROWS_WAVE;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int slab = blockIdx.x;
+  const int c0 = slab * PMF_SIVM_SLAB;
+  const int R = a.R, C = a.C;
+  const int64_t ld = a.ld;
+  const int idx = min(*a.cur, C - 1);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+
+  // ---- the slab's piece of x into LDS (columns >= R: zero) ----------------------------------------------------------
+  {
+    const float* xrow = a.A + (int64_t)max(idx, 0) * ld;
+    float xx = 0.f;
+#pragma unroll
+    for (int q = 0; q < PMF_SIVM_SLAB / 1024; ++q) {
+      const int o = 4 * (tid + 256 * q), c = c0 + o;
+      f32x4 x = zero;
+      if (idx >= 0 && c < R) {
+        x = *reinterpret_cast<const f32x4*>(xrow + c);
+        if (c + 4 > R) {
+#pragma unroll
+          for (int e = 1; e < 4; ++e)
+            if (c + e >= R) x[e] = 0.f;
+        }
+      }
+      *reinterpret_cast<f32x4*>(xs + o) = x;
+      if (METRIC == PMF_SIVM_COSINE) xx += (x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]);
+    }
+    if (METRIC == PMF_SIVM_COSINE) {               // |x|^2 of the slab: lanes, then waves, float64
+      const double w = sivm_wave_sum((double)xx);
+      if (lane == 0) xw[wave] = w;
+    }
+    __syncthreads();
+    if (METRIC == PMF_SIVM_COSINE && blockIdx.y == 0 && tid == 0) a.xpart[slab] = ((xw[0] + xw[1]) + xw[2]) + xw[3];
+  }
+
+  // ---- the wave's rows through the slab -------------------------------------------------------------------------------
+  const int r0 = blockIdx.y * PMF_SIVM_ROWS_WG + wave * NR;
+  const float* rp[NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) rp[j] = a.A + (int64_t)min(r0 + j, C - 1) * ld;   // (rows >= C reread the last row; never written)
+  f32x4 s[NR], nn[NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) { s[j] = zero; nn[j] = zero; }
+  for (int st = 0; st < PMF_SIVM_SLAB / 256; ++st) {
+    const int cb = c0 + 256 * st;
+    if (cb >= R) break;                            // (uniform)
+    const int c = cb + 4 * lane;
+    const f32x4 x = *reinterpret_cast<const f32x4*>(xs + 256 * st + 4 * lane);
+    f32x4 v[NR];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) v[j] = c < R ? *reinterpret_cast<const f32x4*>(rp[j] + c) : zero;
+    if (c < R && c + 4 > R) {                      // the ragged last quad: columns >= R do not contribute
+#pragma unroll
+      for (int j = 0; j < NR; ++j)
+#pragma unroll
+        for (int e = 1; e < 4; ++e)
+          if (c + e >= R) v[j][e] = 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      if (METRIC == PMF_SIVM_L2) {
+        const f32x4 d = v[j] - x;
+        s[j] += d * d;
+      } else if (METRIC == PMF_SIVM_L1) {
+        const f32x4 d = v[j] - x;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[j][e] += fabsf(d[e]);
+      } else {
+        s[j] += v[j] * x;
+        nn[j] += v[j] * v[j];
+      }
+    }
+  }
+
+  // ---- lanes in float64; lane j writes row r0 + j ---------------------------------------------------------------------
+  double out = 0.0, out2 = 0.0;
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const double t = sivm_wave_sum((double)((s[j][0] + s[j][1]) + (s[j][2] + s[j][3])));
+    if (lane == j) out = t;
+    if (METRIC == PMF_SIVM_COSINE) {
+      const double t2 = sivm_wave_sum((double)((nn[j][0] + nn[j][1]) + (nn[j][2] + nn[j][3])));
+      if (lane == j) out2 = t2;
+    }
+  }
+  if (lane < NR && r0 + lane < C) {
+    const int64_t o = (int64_t)slab * a.Cs + r0 + lane;
+    a.part[o] = out;
+    if (METRIC == PMF_SIVM_COSINE) a.part[(int64_t)a.slabs * a.Cs + o] = out2;
+  }
+}
+
+struct SivmRowStepArgs {
+  const double* part;      // as SivmRowArgs
+  const double* xpart;
+  double* dij;             // [C] the recurrence's state
+  double* dsum;
+  double* dsq;
+  int* cur;                // [1] in: the row this round measured against; out: the row of the next round
+  int* select;             // [nsel]
+  double* scal;            // [0] maxd, [1] a = log(maxd)
+  int C, Cs, slabs;
+  int metric;
+  int tpr;                 // threads per row of the slab sum: a power of two <= 64
+  int plain;               // score = dist, state untouched
+  int l;                   // step of the recurrence (sivm.py:181)
+  int take_maxd;           // this is the last plain pass: its best score is maxd
+  int keep_cur;            // the next round measures against the same row ('origin': -1 again)
+  int sel_pos;             // >= 0: select[sel_pos] = the row this round measured against
+  int last_pos;            // >= 0: select[last_pos] = the row of the next round (the last launch)
+};
+
+__global__ __launch_bounds__(256) void k_sivm_rowstep(const SivmRowStepArgs a) {
+  __shared__ double sb[4];
+  __shared__ int ib[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tpr = a.tpr, ql = tid & (tpr - 1), g = tid / tpr, groups = 256 / tpr;
+  const int C = a.C;
+  const int cur_in = *a.cur;
+  const bool cosine = a.metric == PMF_SIVM_COSINE;
+  const int64_t blk = (int64_t)a.slabs * a.Cs;
+
+  double xn = 0.0;                                 // cosine: |x| from the slabs' |x|^2 (threads, lanes, waves: a fixed order)
+  if (cosine) {
+    double t = 0.0;
+    for (int q = tid; q < a.slabs; q += 256) t += a.xpart[q];
+    t = sivm_wave_sum(t);
+    if (lane == 0) sb[wave] = t;
+    __syncthreads();
+    xn = sqrt(((sb[0] + sb[1]) + sb[2]) + sb[3]);
+    __syncthreads();
+  }
+  const double a_log = a.plain ? 0.0 : a.scal[1];
+  const double hl = 0.5 * (double)a.l;
+  double bs = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int rb = 0; rb < C; rb += groups) {         // (uniform trip count: the shuffles below are executed by every lane)
+    const int r = rb + g;
+    double s0 = 0.0, s1 = 0.0;
+    if (r < C) {
+      const double* p = a.part + r;
+      for (int q = ql; q < a.slabs; q += tpr) {
+        s0 += p[(int64_t)q * a.Cs];
+        if (cosine) s1 += p[blk + (int64_t)q * a.Cs];
+      }
+    }
+    for (int x = 1; x < tpr; x <<= 1) {
+      s0 += __shfl_xor(s0, x);
+      s1 += __shfl_xor(s1, x);
+    }
+    if (r < C && ql == 0) {
+      double dist;
+      if (a.metric == PMF_SIVM_L2) dist = sqrt(s0);
+      else if (a.metric == PMF_SIVM_L1) dist = s0;
+      else dist = 1.0 - s0 / (sqrt(s1) * xn + 1e-9);
+      if (a.plain) {
+        sivm_better(bs, bi, dist, r);
+      } else {
+        const double d = log(dist + 1e-8);
+        const double ds_old = a.dsum[r];
+        const double dij = a.dij[r] + d * ds_old;
+        const double ds = ds_old + d;
+        const double dq = a.dsq[r] + d * d;
+        a.dij[r] = dij;
+        a.dsum[r] = ds;
+        a.dsq[r] = dq;
+        sivm_better(bs, bi, dij + a_log * ds - hl * dq, r);
+      }
+    }
+  }
+  sivm_wg_best(bs, bi, sb, ib);
+  if (tid == 0) {
+    const double best = sb[0];
+    const int arg = ((unsigned)ib[0] < (unsigned)C) ? ib[0] : 0;   // (no finite score at all: row 0, nothing outside A is read)
+    const int next = a.keep_cur ? cur_in : arg;
+    if (a.sel_pos >= 0) a.select[a.sel_pos] = cur_in;
+    if (a.take_maxd) { a.scal[0] = best; a.scal[1] = log(best); }
+    if (a.last_pos >= 0) a.select[a.last_pos] = next;
+    *a.cur = next;
+  }
 }
 
 // ---- the H step (aa.py:93-111): min 1/2 x^T (W^T W) x - (W^T v)^T x, x >= 0, sum x = 1, one problem per column ---------------
