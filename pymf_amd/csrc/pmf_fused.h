@@ -11,8 +11,13 @@
 // Waves are autonomous (no barrier inside the loop): H (k x n) and G (k x k) sit
 // read-only in LDS for the whole workgroup; each wave owns a private LDS image of
 // its current V block (16 x n) and W block (16 x k), filled by LDS-DMA
-// (global_load_lds_dwordx4, source-side XOR swizzle) and drained with counted
-// s_waitcnt vmcnt(N).  The epilogue's accumulator registers (C layout) ARE the A
+// (buffer_load_dwordx4 ... lds in the block loop: no vector instruction per
+// request, dma_rsrc / dma16 below; global_load_lds_dwordx4 for H and G in the
+// prologue; source-side XOR swizzle) and drained with counted s_waitcnt vmcnt(N).
+// The W image's last readers are the old W rows (read under the step before the
+// last of phase A) and the last Den fragments, so the next block's W is requested
+// under the last Den step's MFMAs; phase B's first V fragment is read in front of
+// the epilogue.  The epilogue's accumulator registers (C layout) ARE the A
 // operand of phase B: MFMA step j of a 16-row block contracts rows {4q + j}, which
 // is exactly what register j of lane group q holds -- no LDS round trip for W_b.
 // Phase B walks the column panels in the same order phase A does, so panel p of the
@@ -37,6 +42,20 @@
 #define PMF_GLDS16(gsrc, ldst)                                                            \
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc), \
                                    (__attribute__((address_space(3))) void*)(ldst), 16, 0, 0)
+
+// The block loop's LDS-DMA goes out in the BUFFER form (buffer_load_dwordx4 ... lds): the address is descriptor base (SGPRs, one
+// per 16-row block) + per-lane byte offset (a VGPR computed once per wave) + SGPR offset (the column panel) + immediate, so a
+// request costs no vector instruction.  The immediate is added to the LDS address as well as to the source address: the four
+// requests of a V panel share ONE M0 value, the q-th carrying 1024 q, which its lane offset has been reduced by beforehand.
+// A request beyond the descriptor's byte count returns zeros instead of touching memory.
+typedef __attribute__((address_space(3))) void* pmf_lds_ptr;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t dma_rsrc(const char* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, bytes, 0x00020000);   // raw buffer, 32-bit data format
+}
+template <int IMM>
+__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, float* ldst, unsigned voff, int soff) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (pmf_lds_ptr)ldst, 16, (int)voff, soff, IMM, 0);
+}
 
 // Diagnostic build only (-DPMF_STAMPS): per-section cycle sums of one wave (guide section 7,
 // "In-kernel stamps").  Never compiled into the shipped library.
@@ -144,22 +163,29 @@ __global__ __launch_bounds__(256, 1) void k_nmf_fused(const float* __restrict__ 
 
   // LDS-DMA geometry: one instruction = 4 rows x 256 B; lane L fills physical chunk (L & 15)
   // of row 4q + (L >> 4), so it fetches logical chunk (L & 15) ^ row.  Per-lane BYTE offsets
-  // (32-bit) relative to a scalar row base: the source address is SGPR base + VGPR offset.
+  // (32-bit) relative to the block's first byte.  voff[q] is short of the true offset by the 1024 q its request adds as
+  // an immediate (row >= 4 q and a row is at least 256 bytes, so it stays non-negative).
   unsigned voff[4], woff[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int row = 4 * q + (lane >> 4);
     const int c = (lane & 15) ^ vtile_xor(row);   // the W image is read both ways as well (Den fragments, old W rows)
-    voff[q] = (unsigned)(row * NP * 4 + 16 * c);
+    voff[q] = (unsigned)(row * NP * 4 + 16 * c - 1024 * q);
     woff[q] = (unsigned)(row * KP * 4 + 16 * (4 * c < KP ? c : 0));   // beyond k: valid, never read
   }
   const char* Vb = reinterpret_cast<const char*>(V);
   const char* Wb = reinterpret_cast<const char*>(W);
   auto issue_v = [&](int blk, int p, int q) {      // V rows of block blk, panel p, DMA q
-    PMF_GLDS16(Vb + ((size_t)blk * (16 * NP * 4) + (hp + p) * 256) + voff[q], sV + p * 1024 + q * 256);
+    const __amdgpu_buffer_rsrc_t r = dma_rsrc(Vb + (size_t)blk * (16 * NP * 4), 16 * NP * 4);
+    float* dst = sV + p * 1024;
+    const int soff = (hp + p) * 256;
+    if (q == 0) dma16<0>(r, dst, voff[0], soff);
+    else if (q == 1) dma16<1024>(r, dst, voff[1], soff);
+    else if (q == 2) dma16<2048>(r, dst, voff[2], soff);
+    else dma16<3072>(r, dst, voff[3], soff);
   };
   auto issue_w = [&](int blk, int q) {
-    PMF_GLDS16(Wb + (size_t)blk * (16 * KP * 4) + woff[q], sW + q * 256);
+    dma16<0>(dma_rsrc(Wb + (size_t)blk * (16 * KP * 4), 16 * KP * 4), sW + q * 256, woff[q], 0);
   };
 
   f32x4 P[NT][NTP];
@@ -317,6 +343,17 @@ __global__ __launch_bounds__(256, 1) void k_nmf_fused(const float* __restrict__ 
         for (int nt = 0; nt < NT; ++nt) fb[buf][nt] = lds_read4(sG, 16 * nt + i, chunk);
       }
     };
+    // old W rows in the accumulator (C) layout: NT consecutive floats per (lane, j)
+    float wold[NT][4];
+    auto read_wold = [&]() {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int row = 4 * kq + j, col = NT * i + nt;
+          wold[nt][j] = sW[vtile_off(row, col >> 2) + (col & 3)];
+        }
+    };
     // V panel p of this block has landed.  vmcnt counts every later VMEM op in issue order.
     //  clumped:  panels p+1.. (4 DMA each) may still be in flight.
     //  SPREAD :  order per block is [last panel x4 under phase A steps 0..3][W' x4][stores]
@@ -356,13 +393,25 @@ __global__ __launch_bounds__(256, 1) void k_nmf_fused(const float* __restrict__ 
         for (int e = 0; e < 4; ++e)
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt) num[nt] = mfma16(fa[buf][e], fb[buf][nt][e], num[nt]);
-      } else {
+      } else if (s < NSA - 1) {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt) den[nt] = mfma16(fa[buf][e], fb[buf][nt][e], den[nt]);
+      } else {
+        // The last Den step.  Its fragments were the last reads of the W image (the old W rows went out a step ago), so the
+        // next block's W is requested HERE, one piece behind each quarter of the step's MFMAs, not behind the epilogue.
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma unroll
+          for (int nt = 0; nt < NT; ++nt) den[nt] = mfma16(fa[buf][e], fb[buf][nt][e], den[nt]);
+          if (more) issue_w(blk + bstep, e);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
       if (SPREAD && s < 4) issue_v(blk, NPANEL - 1, s);   // this block's last panel, 1 DMA/step
+      if (!SNMF && s == NSA - 2) read_wold();             // (their issue slots lie under this step's MFMAs)
       // issue order inside the step: one LDS read (of step s+1) per 2 MFMAs (of step s), so a
       // read's issue slot hides under an executing MFMA and the last read is >= 6 MFMAs old when
       // the next step needs it; the DMA goes last
@@ -371,6 +420,13 @@ __global__ __launch_bounds__(256, 1) void k_nmf_fused(const float* __restrict__ 
         for (int g = 0; g < NT + 1; ++g) {
           __builtin_amdgcn_sched_group_barrier(0x008, NT >= 4 ? 2 : 1, 0);   // MFMA
           __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                  // DS read
+        }
+        if (!SNMF && s == NSA - 2) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {                                       // the four reads of the old W rows
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
         }
       }
       __builtin_amdgcn_sched_group_barrier(0x008, 4 * NT, 0);                     // remaining MFMAs
@@ -386,22 +442,12 @@ __global__ __launch_bounds__(256, 1) void k_nmf_fused(const float* __restrict__ 
       for (int nt = 0; nt < NT; ++nt) num[nt] += sX[((wv ^ 1) * NT + nt) * 64 + lane];
     }
     PMF_STAMP(ts2);
-    // old W rows in the accumulator (C) layout, then the W image is free: prefetch the next block's
-    float wold[NT][4];
-    if (!SNMF) {
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int row = 4 * kq + j, col = NT * i + nt;       // NT consecutive floats per (lane, j)
-          wold[nt][j] = sW[vtile_off(row, col >> 2) + (col & 3)];
-        }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (more) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) issue_w(blk + bstep, q);
-      }
-    }
+    // phase B's first fragment: its read returns under the epilogue
+    auto load_bf = [&](int s, int buf) {
+      const int p = s >> 2, row = 4 * kq + (s & 3);
+      bf[buf] = vtile_read4(sV + p * 1024, row, i);
+    };
+    load_bf(0, 0);
     PMF_STAMP(ts3);
 
     // ------- epilogue W_b <- (W_b * Num) / (Den + eps), interleaved with S += of the previous block -------
@@ -497,11 +543,6 @@ __global__ __launch_bounds__(256, 1) void k_nmf_fused(const float* __restrict__ 
     // The MFMA column index of a lane is free: P tile (mt, 4p + e) holds columns {64p + 4i + e},
     // so ONE 16-byte read of chunk i of row 4kq + j feeds the four column tiles of a panel step
     // (k_reduce_slabs_tiles undoes the permutation when it scatters into the row-major buffer).
-    auto load_bf = [&](int s, int buf) {
-      const int p = s >> 2, row = 4 * kq + (s & 3);
-      bf[buf] = vtile_read4(sV + p * 1024, row, i);
-    };
-    load_bf(0, 0);
 #pragma unroll
     for (int s = 0; s < NSN; ++s) {
       if (s + 1 < NSN) load_bf(s + 1, (s + 1) & 1);
