@@ -42,6 +42,16 @@ def test_case_matches_the_oracle(pm, name):
     assert abs(mdl.ferr[0] - c["ferr"]) <= gc.device_tol_ferr() * np.linalg.norm(c["data"].astype(np.float64))
 
 
+@pytest.mark.parametrize("name", list(gc.SELECT_CASES))
+def test_selection_of_the_wide_and_panel_cases(pm, name):
+    """Eight operand tiles on every wave, more than one panel per workgroup, a second trip of the panel loop with one and with two
+    row chunks, and more candidates in Gram space than k_greedy_gram has threads (greedy_cases.SELECT_CASES)."""
+    c, mdl = run(pm, name, compute_h=False, compute_err=False)
+    print(name, mdl.select[:8], c["select"][:8], min(c["gaps"]))
+    assert mdl.select == c["select"] and all(type(s) is int for s in mdl.select)
+    assert mdl.W.dtype == np.float32 and np.array_equal(mdl.W, c["data"][:, c["select"]])
+
+
 def test_planted_tie_takes_the_lower_index(pm):
     c, mdl = run(pm, gc.TIE_CASE, compute_h=False, compute_err=False)
     src, dup = gc.tie_columns(gc.spectrum_data(64, 640, 8))
@@ -142,6 +152,20 @@ def test_cabi_alone(pm):
         assert gc.rel_max(ctx.get_h64(), c["H"]) <= gc.device_tol_h()
         assert abs(ctx.frobenius() - c["ferr"]) <= gc.device_tol_ferr() * np.linalg.norm(c["data"].astype(np.float64))
         assert ctx.greedy_select(6).tolist() == c["select"]
+    finally:
+        ctx.close()
+
+
+def test_cabi_widest_operand_twice(pm):
+    """pmf_greedy_select with 64 bases (k_greedy_pass<4> .. <8>): the oracle's list, and the same list from a second call."""
+    from pymf_amd import _lib
+    c = gc.case("80x640_k64")
+    ctx = _lib.Context(_lib.ALGO_GREEDY, 80, 640, 64)
+    try:
+        ctx.set_v_dense(c["data"])
+        first = ctx.greedy_select(64)
+        assert first.dtype == np.int32 and first.tolist() == c["select"]
+        assert np.array_equal(ctx.greedy_select(64), first)
     finally:
         ctx.close()
 

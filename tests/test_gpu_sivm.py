@@ -40,6 +40,32 @@ def test_parity(name):
     assert np.abs(H.sum(axis=0) - 1.0).max() <= 1e-5
 
 
+@pytest.mark.parametrize("name", sorted(sc.PANEL_CASES))
+def test_panel_ranges_select_and_w(name):
+    """Several panels per workgroup in k_sivm_pass, every metric and the origin start: selection and W only (sivm_cases.py)."""
+    c, mdl = device(name, compute_h=False, compute_err=False)
+    print("%s select %s" % (name, mdl.select))
+    assert mdl.select == c["select"]
+    assert all(type(s) is int for s in mdl.select)
+    assert np.array_equal(np.asarray(mdl.W, dtype=np.float32), c["V"][:, c["select"]])
+
+
+def test_panel_ranges_through_sivm_select():
+    """The same ranges from SIVM_CUR's entry point, the column-panel pass forced: among the columns of the 8 x 65 600 data, and
+    among the rows of a 65 600 x 8 copy (the pass then runs on a transposed copy made on the device)."""
+    c = sc.case("8x65600_k3_l2")
+    V = c["V"]
+    for data, transposed in ((V, False), (np.ascontiguousarray(V.T), True)):
+        ctx = _lib.Context(_lib.ALGO_CUR, data.shape[0], data.shape[1], c["k"])
+        try:
+            ctx.set_v_dense(data)
+            got = ctx.sivm_select(c["k"], transposed, 0, 0, path=1)
+            print(transposed, got.tolist())
+            assert got.tolist() == c["select"]
+        finally:
+            ctx.close()
+
+
 def test_compute_h_false_leaves_zeros():
     c, mdl = device("29x300_k6_l2", compute_h=False)
     assert mdl.select == c["select"]
