@@ -42,6 +42,7 @@
  *   pmf_svd_decompose / pmf_svd_get  SVD.factorize, U / S / V  pymf/svd.py:110-158 (algo 12; PCA: pymf/pca.py)
  *   pmf_cur_sqnorms       CUR.sample_probability       pymf/cur.py:84-97 (algo 14)
  *   pmf_cur_compute / pmf_cur_get  CUR.computeUCR, C / U / R  pymf/cur.py:99-120 (CMD: pymf/cmd.py)
+ *   pmf_cur_leverage      CURSL.sample_probability     pymf/cursl.py:65-91 (algo 14)
  *   pmf_greedy_select     self.select of GREEDY        pymf/greedy.py:105-158 (algo 15; GREEDYCUR.sample: pymf/greedycur.py:62-68)
  *
  * Every function returns PMF_OK (0) or a negative status and never throws;
@@ -306,6 +307,18 @@ int pmf_svd_get(pmf_ctx* ctx, double* U, double* S, double* V);
 int pmf_cur_sqnorms(pmf_ctx* ctx, double* row_sq, double* col_sq);
 int pmf_cur_compute(pmf_ctx* ctx, const int32_t* rid, const int32_t* rcnt, int32_t nr, const int32_t* cid, const int32_t* ccnt, int32_t nc);
 int pmf_cur_get(pmf_ctx* ctx, double* C, double* U, double* R);
+
+/* CURSL (pymf/cursl.py: CMD with statistical leverage scores as sampling probabilities) on a CUR / CMD context (algo 14).
+ * pmf_cur_leverage: row_lev [m] = the squared row norms of the leading min(k_rows, rank) left singular vectors of the resident
+ * data, col_lev [n] = the squared column norms of the leading min(k_cols, rank) right singular vectors, float64, unnormalised:
+ * what CURSL.sample_probability divides by k and normalises (cursl.py:66-85; svd.py keeps the triples with an eigenvalue > 1e-8).
+ * Each vector sums to its min(k, rank).  The eigenpairs of the float64 Gram matrix on the short side are cached per V and shared
+ * with pmf_greedy_select; the long side is one read of V on the float64 MFMA (k_lev_f64), the projected singular vectors are
+ * never written out.  A NULL pointer skips that side.  Dense resident data, one rank, k_rows, k_cols >= 1, min(k, rank) <= 128,
+ * min(rows, cols) <= 2432 -- PMF_EINVAL otherwise.  Two calls give the same bits.
+ * pmf_set_option "profile_cur" (0 default: the cross product of pmf_cur_compute, 1: k_lev_f64, 2: k_cur_sqnorms) chooses the
+ * launch that pmf_profile_enable times on a CUR / CMD context. */
+int pmf_cur_leverage(pmf_ctx* ctx, int32_t k_rows, int32_t k_cols, double* row_lev, double* col_lev);
 
 /* GREEDY (algo 15; pymf/greedy.py for dense data, Civril and Magdon-Ismail: W = the num_bases data columns that best reproduce
  * the leading singular subspace, chosen one after the other; H = pinv(W) data).  Dense resident data, one rank, num_bases <= 64,

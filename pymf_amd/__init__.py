@@ -19,10 +19,11 @@ from .pca import PCA          # noqa: F401  
 from .svd import pinv         # noqa: F401  (svd.py:27-45)
 from .cur import CUR          # noqa: F401  
 from .cmd import CMD          # noqa: F401  
+from .cursl import CURSL      # noqa: F401  
 from .greedy import GREEDY    # noqa: F401  
 from .greedycur import GREEDYCUR   # noqa: F401  
 from .sivm_cur import SIVM_CUR     # noqa: F401  
 from . import dist            # noqa: F401
 
-__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "SVD", "PCA", "CUR", "CMD", "GREEDY", "GREEDYCUR", "SIVM_CUR", "pinv", "dist"]
+__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "SVD", "PCA", "CUR", "CMD", "CURSL", "GREEDY", "GREEDYCUR", "SIVM_CUR", "pinv", "dist"]
 __version__ = "0.1.0"

@@ -78,6 +78,7 @@ SYMBOLS = [
     ("pmf_cur_sqnorms", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p]),
     ("pmf_cur_compute", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_int32]),
     ("pmf_cur_get", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    ("pmf_cur_leverage", _c.c_int, [_ctx, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_void_p]),
     ("pmf_stream_begin", _c.c_int, [_ctx, _c.c_uint32, _c.c_int64]),
     ("pmf_stream_tile", _c.c_int, [_ctx, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64]),
     ("pmf_stream_end", _c.c_int, [_ctx, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int32)]),
@@ -442,6 +443,15 @@ class Context(object):
         """CUR / CMD: the row sums (m) and column sums (n) of data**2, float64 (pmf_cur_sqnorms)."""
         row, col = np.zeros(self.m, dtype=np.float64), np.zeros(self.n, dtype=np.float64)
         self._chk(self._lib.pmf_cur_sqnorms(self._h, row.ctypes.data, col.ctypes.data))
+        return row, col
+
+    def cur_leverage(self, k_rows, k_cols, want="rc"):
+        """CURSL: the unnormalised leverage scores, float64 (pmf_cur_leverage): for the rows (m) the squared row norms of the
+        leading min(k_rows, rank) left singular vectors, for the columns (n) the squared column norms of the leading
+        min(k_cols, rank) right singular vectors.  A side not named in `want` ("r", "c") comes back as None."""
+        row = np.zeros(self.m, dtype=np.float64) if "r" in want else None
+        col = np.zeros(self.n, dtype=np.float64) if "c" in want else None
+        self._chk(self._lib.pmf_cur_leverage(self._h, int(k_rows), int(k_cols), *(None if a is None else a.ctypes.data for a in (row, col))))
         return row, col
 
     def cur_compute(self, rid, rcnt, cid, ccnt):

@@ -40,6 +40,7 @@
 #include "pmf_aa.h"
 #include "pmf_svd.h"
 #include "pmf_cur.h"
+#include "pmf_lev.h"
 #include "pmf_greedy.h"
 
 // the internal host code, by concern (each header: one anonymous-namespace block; the order is the dependency order)
@@ -674,6 +675,12 @@ int pmf_cur_sqnorms(pmf_ctx* c, double* row_sq, double* col_sq) {
   return cur_sqnorms(c, row_sq, col_sq);
 }
 
+int pmf_cur_leverage(pmf_ctx* c, int32_t k_rows, int32_t k_cols, double* row_lev, double* col_lev) {
+  if (c && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_cur_leverage: CUR / CMD contexts only");
+  PMFCHK(need(c, true, false, false));
+  return cur_leverage(c, k_rows, k_cols, row_lev, col_lev);
+}
+
 int pmf_cur_compute(pmf_ctx* c, const int32_t* rid, const int32_t* rcnt, int32_t nr, const int32_t* cid, const int32_t* ccnt, int32_t nc) {
   if (c && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_cur_compute: CUR / CMD contexts only");
   PMFCHK(need(c, true, false, false));
@@ -1271,6 +1278,13 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
     if (c->algo != PMF_ALGO_SIVM && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "profile_sivm_rows: SIVM and CUR / CMD contexts only");
     if (value != 0 && value != 1) return fail(c, PMF_EINVAL, "profile_sivm_rows: 0 or 1");
     c->opt_profile_sivm_rows = (int)value;
+    choose_stat_site(c, false);
+    return PMF_OK;
+  }
+  if (std::strcmp(name, "profile_cur") == 0) {
+    if (c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "profile_cur: CUR / CMD contexts only");
+    if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "profile_cur: 0 (the cross product), 1 (k_lev_f64) or 2 (k_cur_sqnorms)");
+    c->opt_profile_cur = (int)value;
     choose_stat_site(c, false);
     return PMF_OK;
   }

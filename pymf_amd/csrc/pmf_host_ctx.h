@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_SIVM_ROWS, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_SIVM_ROWS, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY, SITE_CUR_LEV, SITE_CUR_SQNORMS };
 
 struct KernelStat {
   std::string name = "none";
@@ -193,6 +193,7 @@ struct pmf_ctx {
   int cur_nr = 0, cur_nc = 0;
   std::vector<double> cur_dc, cur_dr, cur_U;
   bool cur_valid = false;       // they belong to the current V.  <- V
+  int opt_profile_cur = 0;      // pmf_set_option("profile_cur"): pmf_profile_enable times 0 the cross product, 1 k_lev_f64, 2 k_cur_sqnorms
   // GREEDY / GREEDYCUR (pmf_greedy.h): the float64 Gram matrix on the short side of V and the rows of its eigenvectors ([qp][qp]
   // each), on the host the eigenvalues and the indices of those above svd.py's 1e-8 cut in descending order; pinv(W)^T [mp][KP]
   // float32, the operand of H = pinv(W) data.  The selection itself is read through dSvSel / sv_have_select (SIVM's).

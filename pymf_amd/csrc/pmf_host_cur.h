@@ -20,14 +20,105 @@ int cur_sqnorms(pmf_ctx* c, double* row_sq, double* col_sq) {
   PMFCHK(talloc(c, tmp, &rowpart, (size_t)npanels * mp));
   PMFCHK(talloc(c, tmp, &colpart, (size_t)nblocks * np));
   PMFCHK(talloc(c, tmp, &out, (size_t)(mp + np)));
+  stat_begin(c, SITE_CUR_SQNORMS);
   hipLaunchKernelGGL(k_cur_sqnorms, dim3((unsigned)((int64_t)nblocks * npanels)), dim3(256), 0, c->stream, (const float*)c->dV, np, mp, npanels,
                      rowpart, colpart);
+  stat_end(c, SITE_CUR_SQNORMS);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_cur_sqnorms_reduce, dim3((unsigned)((mp + np) / 64)), dim3(1024), 0, c->stream, (const double*)rowpart, npanels, mp,
                      (const double*)colpart, nblocks, np, out);
   HIPCHK(c, hipGetLastError());
   if (row_sq) HIPCHK(c, hipMemcpyAsync(row_sq, out, (size_t)c->m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (col_sq) HIPCHK(c, hipMemcpyAsync(col_sq, out + mp, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
+  return PMF_OK;
+}
+
+int greedy_eig(pmf_ctx* c);   // pmf_host_greedy.h, further down the include order
+
+template <bool TRANS, int NT>
+void lev_launch_t(pmf_ctx* c, const double* Pm, int qp, int64_t lp, double* lev) {
+  hipLaunchKernelGGL((k_lev_f64<TRANS, NT>), dim3((unsigned)((lp + PMF_LEV_PANEL - 1) / PMF_LEV_PANEL)), dim3(256), 0, c->stream,
+                     (const float*)c->dV, (int64_t)c->np, Pm, qp, lp, lev);
+}
+template <bool TRANS>
+int lev_launch(pmf_ctx* c, int nt, const double* Pm, int qp, int64_t lp, double* lev) {
+  switch (nt) {
+    case 1: lev_launch_t<TRANS, 1>(c, Pm, qp, lp, lev); break;
+    case 2: lev_launch_t<TRANS, 2>(c, Pm, qp, lp, lev); break;
+    case 3: lev_launch_t<TRANS, 3>(c, Pm, qp, lp, lev); break;
+    case 4: lev_launch_t<TRANS, 4>(c, Pm, qp, lp, lev); break;
+    case 5: lev_launch_t<TRANS, 5>(c, Pm, qp, lp, lev); break;
+    case 6: lev_launch_t<TRANS, 6>(c, Pm, qp, lp, lev); break;
+    case 7: lev_launch_t<TRANS, 7>(c, Pm, qp, lp, lev); break;
+    case 8: lev_launch_t<TRANS, 8>(c, Pm, qp, lp, lev); break;
+    default: return fail(c, PMF_EINVAL, "pmf_cur_leverage: more than 128 singular vectors");
+  }
+  HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+// cursl.py:66-85 without the division by k and the normalisation: row_lev [m] = the squared row norms of the leading
+// min(k_rows, rank) left singular vectors, col_lev [n] = the squared column norms of the leading min(k_cols, rank) right singular
+// vectors, float64, from the cached eigenpairs of the Gram matrix on the short side (greedy_eig).  The eigenvector side is
+// k_lev_eig, the long side one read of V by k_lev_f64 (pmf_lev.h).  Either pointer may be null.
+int cur_leverage(pmf_ctx* c, int k_rows, int k_cols, double* row_lev, double* col_lev) {
+  PMFCHK(cur_check(c, "pmf_cur_leverage"));
+  if (k_rows < 1 || k_cols < 1) return fail(c, PMF_EINVAL, "pmf_cur_leverage: k_rows, k_cols >= 1");
+  if (std::min<int64_t>(c->m, c->n) > PMF_SVD_MAX_RANK) return fail(c, PMF_EINVAL, "pmf_cur_leverage: min(rows, cols) > 2432 is not supported by this build");
+  PMFCHK(greedy_eig(c));
+  const bool left = c->m > c->n;                        // the eigenvectors are the right singular vectors: the columns' side
+  const int rank = (int)c->gr_ord.size();
+  const int q = (int)(left ? c->n : c->m), qp = left ? c->np : (int)c->mp;
+  const int64_t lp = left ? c->mp : (int64_t)c->np;
+  double* out_long = left ? row_lev : col_lev;
+  double* out_eig = left ? col_lev : row_lev;
+  const int64_t n_long = left ? c->m : c->n;
+  // (a side that is not asked for takes no vectors: nothing is checked, sized or launched for it)
+  const int kk_long = out_long ? std::min(left ? k_rows : k_cols, rank) : 0, kk_eig = out_eig ? std::min(left ? k_cols : k_rows, rank) : 0;
+  if (kk_long > PMF_LEV_MAX_K || kk_eig > PMF_LEV_MAX_K)
+    return fail(c, PMF_EINVAL, "pmf_cur_leverage: min(k, rank) > 128 is not supported by this build");
+  const int kmax = std::max(std::max(kk_long, kk_eig), 1), nt = std::max(1, (kk_long + 15) / 16);
+  std::vector<double> sv((size_t)kmax, 1.0);
+  for (int l = 0; l < std::min(kmax, rank); ++l) sv[(size_t)l] = std::sqrt(c->gr_ev[(size_t)c->gr_ord[(size_t)l]]);
+  DevTemps tmp;
+  int* order = nullptr;
+  double *dsv = nullptr, *Pm = nullptr, *lev = nullptr;
+  const int64_t pm_elems = kk_long > 0 ? (int64_t)(qp / 64) * nt * 1024 : 0;
+  PMFCHK(talloc(c, tmp, &order, (size_t)kmax));
+  PMFCHK(talloc(c, tmp, &dsv, (size_t)kmax));
+  if (pm_elems > 0) PMFCHK(talloc(c, tmp, &Pm, (size_t)pm_elems));
+  PMFCHK(talloc(c, tmp, &lev, (size_t)(lp + qp)));       // the long side, then the eigenvector side (zero filled: kk = 0 leaves zeros)
+  if (rank > 0) {
+    HIPCHK(c, hipMemcpyAsync(order, c->gr_ord.data(), (size_t)std::min(kmax, rank) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dsv, sv.data(), (size_t)kmax * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  if (kk_long > 0) {
+    if (left) hipLaunchKernelGGL(k_lev_gather<false>, dim3(elem_grid(pm_elems)), dim3(256), 0, c->stream, (const double*)c->dGrQT, qp, q, kk_long, nt,
+                                 (const int*)order, (const double*)dsv, pm_elems, Pm);
+    else hipLaunchKernelGGL(k_lev_gather<true>, dim3(elem_grid(pm_elems)), dim3(256), 0, c->stream, (const double*)c->dGrQT, qp, q, kk_long, nt,
+                            (const int*)order, (const double*)dsv, pm_elems, Pm);
+    HIPCHK(c, hipGetLastError());
+    if (c->profile && c->stat.site == SITE_CUR_LEV) {       // the record of the launch at hand (choose_stat_site only names the site)
+      char buf[48];
+      snprintf(buf, sizeof(buf), "k_lev_f64<%s,%d>", left ? "false" : "true", nt);
+      c->stat.name = buf;
+      c->stat.flops = 2.0 * (double)c->m * (double)c->n * kk_long;
+      c->stat.exec_flops = 2.0 * (double)c->mp * (double)c->np * (16.0 * nt);
+      c->stat.bytes = 4.0 * (double)c->mp * (double)c->np + 8.0 * (double)lp;     // V once, one double per position (P from L2)
+    }
+    stat_begin(c, SITE_CUR_LEV);
+    const int rc = left ? lev_launch<false>(c, nt, Pm, qp, lp, lev) : lev_launch<true>(c, nt, Pm, qp, lp, lev);
+    stat_end(c, SITE_CUR_LEV);
+    PMFCHK(rc);
+  }
+  if (kk_eig > 0) {
+    hipLaunchKernelGGL(k_lev_eig, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->dGrQT, qp, q, kk_eig,
+                       (const int*)order, lev + lp);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (out_long) HIPCHK(c, hipMemcpyAsync(out_long, lev, (size_t)n_long * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (out_eig) HIPCHK(c, hipMemcpyAsync(out_eig, lev + lp, (size_t)q * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
   return PMF_OK;
 }

@@ -44,6 +44,14 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.flops = 2.0 * m * n * q;                                   // the whole Gram matrix ...
     st.exec_flops = m * n * (q + 64.0);                           // ... of which the upper block triangle is formed
     st.bytes = 4.0 * (double)c->mp * (double)c->np;              // V once
+  } else if (c->algo == PMF_ALGO_CUR && c->opt_profile_cur == 1) {
+    st.site = SITE_CUR_LEV;                                       // the long-side leverage pass: cur_leverage writes the instantiation's name
+    st.name = "k_lev_f64";                                        // and the flops and bytes of the call (they depend on its k)
+  } else if (c->algo == PMF_ALGO_CUR && c->opt_profile_cur == 2) {
+    st.site = SITE_CUR_SQNORMS;
+    st.name = "k_cur_sqnorms";
+    st.flops = st.exec_flops = 3.0 * m * n;                       // one square, a row sum and a column sum per value
+    st.bytes = 4.0 * (double)c->mp * (double)c->np + 8.0 * (double)c->mp * (double)c->np * (1.0 / 256.0 + 1.0 / 64.0);   // V once, the partials
   } else if (c->algo == PMF_ALGO_CUR) {
     st.site = SITE_CUR;                                           // (nr = nc = the context's k assumed: the call may pass fewer)
     const bool trans = c->m > c->n;
