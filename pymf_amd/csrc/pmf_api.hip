@@ -62,6 +62,7 @@
 #include "pmf_host_cur.h"
 #include "pmf_host_greedy.h"
 #include "pmf_host_factorize.h"
+#include "pmf_host_algos.h"
 
 // =============================================================================================
 extern "C" {
@@ -87,61 +88,24 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                    int32_t rank, int32_t nranks, const void* nccl_id) {
   if (!out) return fail(nullptr, PMF_EINVAL, "out is NULL");
   *out = nullptr;
-  if (algo < 0 || algo > 15 || algo == 7 || algo == 9 || algo == 13)
+  if (algo < 0 || algo >= kAlgoCount || !kAlgos[algo].family)
     return fail(nullptr, PMF_EINVAL, "algo must be 0 (NMF), 1 (NMFALS), 2 (SNMF), 3 (BNMF), 4 (RNMF), 5 (CNMF), 6 (Kmeans), 8 (Cmeans), 10 (SIVM), 11 (AA), 12 (PCA / SVD), 14 (CUR / CMD) or 15 (GREEDY)");
   if (m_local < 1 || n < 1 || k < 1) return fail(nullptr, PMF_EINVAL, "m, n, k must be >= 1");
-  if (algo == PMF_ALGO_CNMF) {  // C = V^T V is n x n float64 (128 MiB at the limit); the k x k factors on one float64 MFMA tile row
-    if (n > 4096) return fail(nullptr, PMF_EINVAL, "CNMF: n (samples) > 4096 is not supported by this build");
-    if (k > 128) return fail(nullptr, PMF_EINVAL, "CNMF: num_bases > 128 is not supported by this build");
-    if (k > n) return fail(nullptr, PMF_EINVAL, "CNMF: num_bases > n (the k-means initialisation samples num_bases columns)");
-    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "CNMF: one rank only in this build");
-  }
-  const bool cluster = algo == PMF_ALGO_KMEANS || algo == PMF_ALGO_CMEANS;
-  if (cluster) {                // k_cluster_pass holds one column's distances to all bases in the registers of four lanes
-    if (k > 128) return fail(nullptr, PMF_EINVAL, "Kmeans / Cmeans: num_bases > 128 is not supported by this build");
-    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "Kmeans / Cmeans: one rank only in this build");
-  }
-  if (algo == PMF_ALGO_SIVM) {  // the H step's QPs run on the kernels of num_bases <= 64; k_sivm_pass stages one column of V in LDS
-    if (k > 64) return fail(nullptr, PMF_EINVAL, "SIVM: num_bases > 64 is not supported by this build");
-    if (m_local > PMF_SIVM_MAX_M) return fail(nullptr, PMF_EINVAL, "SIVM: data_dimension > 16384 is not supported by this build");
-    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "SIVM: one rank only in this build");
-  }
-  if (algo == PMF_ALGO_AA) {    // the H step is SIVM's; a base's corral holds an affinely independent set of data columns: at most min(m + 1, n)
-    if (k > 64) return fail(nullptr, PMF_EINVAL, "AA: num_bases > 64 is not supported by this build");
-    if (std::min<int64_t>(m_local + 1, n) > PMF_AA_MAX_CORRAL)
-      return fail(nullptr, PMF_EINVAL, "AA: min(data_dimension + 1, num_samples) > 128 (the corral bound) is not supported by this build");
-    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "AA: one rank only in this build");
-  }
-  if (algo == PMF_ALGO_PCA) {   // the Gram matrix on the short side goes through the full Jacobi solver; U and V travel as bases of the product paths
-    if (std::min<int64_t>(m_local, n) > PMF_SVD_MAX_RANK)
-      return fail(nullptr, PMF_EINVAL, "PCA / SVD: min(rows, cols) > 2432 is not supported by this build");
-    if (k < std::min<int64_t>(m_local, n))
-      return fail(nullptr, PMF_EINVAL, "PCA / SVD: the context's base count must be at least min(rows, cols) (the largest possible rank)");
-    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "PCA / SVD: one rank only in this build");
-  }
-  if (algo == PMF_ALGO_CUR) {   // the sampled rows and columns are two 64-wide tiles of k_prod_f64 and one 128-wide block of W and H
-    if (k > PMF_CUR_MAX_RANK) return fail(nullptr, PMF_EINVAL, "CUR / CMD: more than 128 sampled rows or columns are not supported by this build");
-    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "CUR / CMD: one rank only in this build");
-  }
-  if (algo == PMF_ALGO_GREEDY) {   // the staged operand [B' | Q] of k_greedy_pass has 2 k - 1 <= 127 columns; the short side goes through the Jacobi solver
-    if (k > PMF_GREEDY_MAX_BASES) return fail(nullptr, PMF_EINVAL, "GREEDY: num_bases > 64 is not supported by this build");
-    if (std::min<int64_t>(m_local, n) > PMF_SVD_MAX_RANK)
-      return fail(nullptr, PMF_EINVAL, "GREEDY: min(rows, cols) > 2432 is not supported by this build");
-    if (nranks > 1) return fail(nullptr, PMF_EINVAL, "GREEDY: one rank only in this build");
-  }
+  const AlgoRow& row = kAlgos[algo];
+  if (const char* over = row.limits ? row.limits(m_local, n, k) : nullptr) return fail(nullptr, PMF_EINVAL, over);   // (the family's own limits before the general ones)
+  if (row.one_rank && nranks > 1) return fail(nullptr, PMF_EINVAL, std::string(row.family) + ": one rank only in this build");
   // The reference has no limit on num_bases (nmf.py:116-120); the generic kernels beyond 128 bases have been checked against
   // the float64 oracles at 1 500, 2 304 and 2 432 bases (tests/sweeps/bigk_limit_probe.py, tests/test_gpu_bigk.py); beyond 2 432 (19 blocks of 128)
   // the 16-column block of H that k_nmf_h and k_trace_terms keep in LDS (64 bytes per basis) no longer fits the 160 KiB.  NMFALS /
-  // NMFNNLS beyond 128 bases solve one variable at a time (k_nnqp_big) and stay at 1 024.
-  if (k > (algo == PMF_ALGO_NMFALS ? 1024 : 2432))
-    return fail(nullptr, PMF_EINVAL, algo == PMF_ALGO_NMFALS ? "num_bases > 1024 is not supported for NMFALS / NMFNNLS by this build"
-                                                             : "num_bases > 2432 is not supported by this build");
+  // NMFNNLS beyond 128 bases solve one variable at a time (k_nnqp_big) and stay at 1 024 (nmfals_limits).
+  if (k > 2432) return fail(nullptr, PMF_EINVAL, "num_bases > 2432 is not supported by this build");
   if (n > (1 << 24)) return fail(nullptr, PMF_EINVAL, "n too large");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(nullptr, PMF_EINVAL, "bad rank/nranks");
   if (nranks > 1 && !nccl_id) return fail(nullptr, PMF_EINVAL, "nccl_id required when nranks > 1");
   pmf_ctx* c = new (std::nothrow) pmf_ctx();
   if (!c) return fail(nullptr, PMF_ENOMEM, "host allocation failed");
   c->algo = algo; c->m = m_local; c->n = n; c->k = k; c->device = device; c->rank = rank; c->nranks = nranks;
+  const bool cluster = is_cluster(c);   // (no n-sized product buffers: pmf_cluster.h has its own)
   c->mp = round_up(m_local, 64);
   c->np = (int)round_up(n, 64);
   c->NT = k <= 16 ? 1 : k <= 32 ? 2 : k <= 64 ? 4 : 8;
@@ -192,7 +156,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
     PMFCHK(dalloc(c, &c->dH, (size_t)c->KP * c->np));
     PMFCHK(dalloc(c, &c->dG, (size_t)c->KP * c->KP));
     PMFCHK(dalloc(c, &c->dGd, (size_t)c->KP * c->KP));
-    if (!cluster) PMFCHK(dalloc(c, &c->dPS, (size_t)ps_elems(c)));   // (Kmeans / Cmeans: no n-sized product buffers, pmf_cluster.h has its own)
+    if (!cluster) PMFCHK(dalloc(c, &c->dPS, (size_t)ps_elems(c)));
     if (cluster) {
       PMFCHK(cluster_alloc(c));
     } else if (c->nb == 1) {
@@ -243,13 +207,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
                                                                            : algo == PMF_ALGO_RNMF ? FUSED_RNMF
                                                                                                    : FUSED_NMF))
                                : std::string("tiled");
-  if (algo == PMF_ALGO_CNMF) c->path = "cnmf_gram";
-  if (cluster) c->path = "cluster_panels";
-  if (algo == PMF_ALGO_SIVM) c->path = "sivm_panels";
-  if (algo == PMF_ALGO_AA) c->path = "aa_pricing";
-  if (algo == PMF_ALGO_PCA) c->path = "svd_gram_f64";
-  if (algo == PMF_ALGO_CUR) c->path = "cur_cross_f64";
-  if (algo == PMF_ALGO_GREEDY) c->path = "greedy_panels";
+  if (row.path) c->path = row.path;
   choose_stat_site(c, false);
   *out = c;
   return PMF_OK;
@@ -469,122 +427,50 @@ int pmf_get_h_f32(pmf_ctx* c, float* H) {
   return download_padded(c, H, c->n, c->dH, c->np, c->k, c->n);
 }
 
-int pmf_update_w(pmf_ctx* c) {
-  if (c && c->algo == PMF_ALGO_CNMF) return PMF_OK;   // cnmf.py:70-76: both hooks are no-ops (the updates live in factorize)
-  if (c && is_cluster(c)) {                            // (the W step reads the assignment / H, not W: kmeans.py:82-87, cmeans.py:83-86)
-    PMFCHK(need(c, true, c->algo == PMF_ALGO_KMEANS, c->algo == PMF_ALGO_CMEANS));   // (Kmeans keeps the columns of centres with < 2 members)
-    PMFCHK(cluster_update_w(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PMF_OK;
-  }
-  if (c && c->algo == PMF_ALGO_SIVM) {                 // (the selection reads the data alone: sivm.py:145-201)
-    PMFCHK(need(c, true, false, false));
-    if (c->v_csr) return fail(c, PMF_EINVAL, "SIVM: dense data only");
-    PMFCHK(sivm_update_w(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PMF_OK;
-  }
-  if (c && c->algo == PMF_ALGO_AA) {                   // (W_hat = data pinv(H): the W step reads the data and H, aa.py:113-134)
-    PMFCHK(need(c, true, false, true));
-    if (c->v_csr) return fail(c, PMF_EINVAL, "AA: dense data only");
-    PMFCHK(aa_update_w(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PMF_OK;
-  }
-  if (c && c->algo == PMF_ALGO_GREEDY) {               // (the selection reads the data alone: greedy.py:88-170)
-    PMFCHK(need(c, true, false, false));
-    PMFCHK(greedy_update_w(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PMF_OK;
-  }
-  if (c && c->algo == PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "CUR / CMD: no W step (pmf_cur_compute is the decomposition)");
-  if (c && c->algo == PMF_ALGO_PCA) {                  // (the decomposition reads the data alone: pca.py:93-108)
-    PMFCHK(need(c, true, false, false));
-    PMFCHK(pca_update_w(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PMF_OK;
-  }
-  PMFCHK(need(c, true, true, true));
-  PMFCHK(do_update_w(c));
+// pmf_update_w / pmf_update_h: the family's step (kAlgos), with what it reads checked first
+static int run_step(pmf_ctx* c, bool w_step) {
+  if (!c) return PMF_EINVAL;
+  if (c->algo == PMF_ALGO_CNMF) return PMF_OK;   // cnmf.py:70-76: both hooks are no-ops (the updates live in factorize)
+  const AlgoRow& a = algo_row(c);
+  int (*step)(pmf_ctx*) = w_step ? a.update_w : a.update_h;
+  if (!step) return refuse_step(c, w_step ? "W step" : "H step");
+  const Operands r = w_step ? a.reads_w : a.reads_h;
+  PMFCHK(need(c, r.v, r.w, r.h));
+  if (c->v_csr && (w_step ? a.dense_w : a.dense_h)) return fail(c, PMF_EINVAL, std::string(a.family) + ": dense data only");
+  PMFCHK(step(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  PMFCHK(ipc_check(c));
-  return check_singular(c);
+  if (!a.nmf_family) return PMF_OK;
+  PMFCHK(ipc_check(c));                          // the NMF family: the exchange's verdict, and the inverse's behind a W step
+  return w_step ? check_singular(c) : PMF_OK;
 }
-int pmf_update_h(pmf_ctx* c) {
-  if (c && c->algo == PMF_ALGO_CNMF) return PMF_OK;
-  if (c && is_cluster(c)) {
-    PMFCHK(need(c, true, true, false));
-    PMFCHK(cluster_update_h(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PMF_OK;
-  }
-  if (c && c->algo == PMF_ALGO_SIVM) {
-    PMFCHK(need(c, true, true, false));
-    PMFCHK(sivm_update_h(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PMF_OK;
-  }
-  if (c && c->algo == PMF_ALGO_AA) {                   // aa.py:93-111, the step SIVM inherits
-    PMFCHK(need(c, true, true, false));
-    if (c->v_csr) return fail(c, PMF_EINVAL, "AA: dense data only");
-    c->g_valid = false;                                // (the step forms W^T W where H H^T was)
-    PMFCHK(sivm_update_h(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PMF_OK;
-  }
-  if (c && c->algo == PMF_ALGO_GREEDY) {               // greedy.py:82-86
-    PMFCHK(need(c, true, true, false));
-    PMFCHK(greedy_update_h(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PMF_OK;
-  }
-  if (c && c->algo == PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "CUR / CMD: no H step (pmf_cur_compute is the decomposition)");
-  if (c && c->algo == PMF_ALGO_PCA) {                  // pca.py:90-91
-    PMFCHK(need(c, true, true, false));
-    PMFCHK(pca_update_h(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PMF_OK;
-  }
-  PMFCHK(need(c, true, true, true));
-  PMFCHK(do_update_h(c));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return ipc_check(c);
-}
+int pmf_update_w(pmf_ctx* c) { return run_step(c, true); }
+int pmf_update_h(pmf_ctx* c) { return run_step(c, false); }
 int pmf_frobenius(pmf_ctx* c, double* out) {
   PMFCHK(need(c, true, true, true));
   if (!out) return fail(c, PMF_EINVAL, "out is NULL");
-  if (c->algo == PMF_ALGO_CNMF) {
-    PMFCHK(cnmf_ready(c));
-    return cnmf_error(c, false, out);
-  }
-  if (is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA || c->algo == PMF_ALGO_CUR || c->algo == PMF_ALGO_GREEDY) return frobenius_direct(c, out);
-  if (c->algo == PMF_ALGO_PCA) return pca_error(c, out);
-  PMFCHK(do_frobenius(c, out));
-  return ipc_check(c);
+  return algo_row(c).frobenius(c, out);
 }
 
 int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, double* ferr,
                   int32_t* iters_done, int32_t* converged_at) {
   const bool cw = flags & PMF_COMPUTE_W, ch = flags & PMF_COMPUTE_H, ce = flags & PMF_COMPUTE_ERR;
-  if (c && c->algo == PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "CUR / CMD: no iteration (pmf_cur_compute is the decomposition)");
-  if (c && (c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_PCA || c->algo == PMF_ALGO_GREEDY)) PMFCHK(need(c, true, !cw, !ch));   // (either step writes its factor from scratch)
-  else if (c && c->algo == PMF_ALGO_AA) PMFCHK(need(c, true, !cw, cw || !ch));   // (the W step reads H, the H step W)
-  else PMFCHK(need(c, true, true, true));
+  if (!c) return PMF_EINVAL;
+  const AlgoRow& a = algo_row(c);
+  if (a.instead) return refuse_step(c, "iteration");
+  const Operands r = a.loop_reads(cw, ch);
+  PMFCHK(need(c, r.v, r.w, r.h));
   if (niter < 0 || (ce && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
   if (iters_done) *iters_done = 0;
   if (converged_at) *converged_at = -1;
-  if (c->algo == PMF_ALGO_SIVM) { SivmLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
-  if (c->algo == PMF_ALGO_PCA) { PcaLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
-  if (c->algo == PMF_ALGO_GREEDY) { GreedyLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
-  if (c->algo == PMF_ALGO_AA) {
-    if (c->v_csr) return fail(c, PMF_EINVAL, "AA: dense data only");
-    AaLoopSteps s{cw, ch};
-    return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at);
-  }
-  if (is_cluster(c)) { ClusterLoopSteps s{cw, ch}; return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at); }
   if (c->algo == PMF_ALGO_CNMF) {
     PMFCHK(cnmf_ready(c));
     CnmfLoopSteps s{cw, ch, niter};
+    return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at);
+  }
+  if (!a.nmf_family) {           // W step, then H step, iteration by iteration
+    // (a family that takes dense data in both steps refuses whichever of them are on)
+    if (c->v_csr && a.dense_w && a.dense_h) return fail(c, PMF_EINVAL, std::string(a.family) + ": dense data only");
+    TableLoopSteps s{a, cw, ch};
     return factorize_loop(c, s, niter, ce, conv_eps, ferr, iters_done, converged_at);
   }
   WPipeGuard wguard{c};
@@ -766,7 +652,7 @@ int pmf_rnmf_set_s_f32(pmf_ctx* c, const float* S) {
 int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (c) c->hd_synced = false;
   if (!c) return PMF_EINVAL;
-  if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF || is_cluster(c) || c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_AA || c->algo == PMF_ALGO_PCA || c->algo == PMF_ALGO_CUR || c->algo == PMF_ALGO_GREEDY)   // (the reference's RNMF keeps S, an in-memory array of data's shape: rnmf.py:94-98)
+  if (!algo_row(c).streamable)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (!c->have_w || !c->have_h) return fail(c, PMF_EINVAL, "pmf_stream_begin: W and H must be set");
   if (max_tile_rows < 1) return fail(c, PMF_EINVAL, "pmf_stream_begin: max_tile_rows must be >= 1");

@@ -19,7 +19,7 @@ int aa_corral_ld(const pmf_ctx* c) { return (int)std::min<int64_t>(c->m + 1, c->
 
 int aa_alloc(pmf_ctx* c) {
   if (c->dAaX) return PMF_OK;
-  panel_partition(c);                           // sv_wgs, sv_ppw
+  panel_partition(c->np / 64, PMF_CL_MAX_WGS, &c->sv_ppw, &c->sv_wgs);
   const int LD = aa_corral_ld(c);
   const size_t E = (size_t)c->mp * c->KP;
   PMFCHK(dalloc(c, &c->dAaWhat, E));
@@ -144,22 +144,10 @@ int aa_update_w(pmf_ctx* c) {
   return PMF_OK;
 }
 
-// pmf_factorize for AA: NMF.factorize's iteration (W step, then H step), no free-running form, the direct residual
-struct AaLoopSteps {
-  bool cw, ch;
-  int iterate(pmf_ctx* c, int) {
-    if (cw) PMFCHK(aa_update_w(c));
-    if (ch) {
-      c->g_valid = false;                       // (the step forms W^T W where H H^T was)
-      PMFCHK(sivm_update_h(c));
-    }
-    return PMF_OK;
-  }
-  int error(pmf_ctx* c, int, double* out) { return frobenius_direct(c, out); }
-  bool may_free_run(const pmf_ctx*, int, double) const { return false; }
-  int enqueue(pmf_ctx* c, int, int, int, double) { return fail(c, PMF_EINVAL, "AA: no free-running loop"); }
-  void rewind(pmf_ctx*, int, int) {}
-  int close(pmf_ctx*) { return PMF_OK; }
-};
+// AA.update_h (aa.py:93-111): the step SIVM inherits
+int aa_update_h(pmf_ctx* c) {
+  c->g_valid = false;                           // (the step forms W^T W where H H^T was)
+  return sivm_update_h(c);
+}
 
 }  // namespace

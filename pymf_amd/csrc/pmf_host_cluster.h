@@ -9,14 +9,19 @@ namespace {
 // (cl_sums_valid); an update_w that no pass preceded (H from the caller, Cmeans' random H0) forms the sums alone first.
 inline bool is_cluster(const pmf_ctx* c) { return c->algo == PMF_ALGO_KMEANS || c->algo == PMF_ALGO_CMEANS; }
 
+// contiguous ranges of 64-column panels over at most `cap` workgroups: the panels each owns and how many there are
+// (k_cluster_pass, k_sivm_pass, k_aa_price, k_greedy_pass)
+void panel_partition(int npanels, int cap, int* ppw, int* wgs) {
+  const int want = std::min(npanels, cap);
+  *ppw = (npanels + want - 1) / want;
+  *wgs = (npanels + *ppw - 1) / *ppw;
+}
+
 int cluster_alloc(pmf_ctx* c) {
   if (c->dClNum) return PMF_OK;
-  const int npanels = c->np / 64;
   // a slab of mp x KP floats per workgroup: at most PMF_CL_MAX_WGS of them and 2 GiB in all (few, tall slabs when m >> n)
   const int64_t by_mem = std::max<int64_t>(1, ((int64_t)1 << 31) / (c->mp * c->KP * (int64_t)sizeof(float)));
-  const int want = (int)std::min<int64_t>(std::min(npanels, PMF_CL_MAX_WGS), by_mem);
-  c->cl_ppw = (npanels + want - 1) / want;
-  c->cl_wgs = (npanels + c->cl_ppw - 1) / c->cl_ppw;
+  panel_partition(c->np / 64, (int)std::min<int64_t>(PMF_CL_MAX_WGS, by_mem), &c->cl_ppw, &c->cl_wgs);
   PMFCHK(dalloc(c, &c->dClNum, (size_t)c->cl_wgs * c->mp * c->KP));
   PMFCHK(dalloc(c, &c->dClDen, (size_t)c->cl_wgs * c->KP));
   PMFCHK(dalloc(c, &c->dClErr, (size_t)c->cl_wgs * 2));
@@ -104,20 +109,5 @@ int cluster_error(pmf_ctx* c, double* out) {
   *out = std::sqrt(t[0]);
   return PMF_OK;
 }
-
-// pmf_factorize for Kmeans / Cmeans: the steps of the loop of nmf.py:182-202 (pmf_host_loop.h); no free-running form
-struct ClusterLoopSteps {
-  bool cw, ch;
-  int iterate(pmf_ctx* c, int) {
-    if (cw) PMFCHK(cluster_update_w(c));
-    if (ch) PMFCHK(cluster_update_h(c));
-    return PMF_OK;
-  }
-  int error(pmf_ctx* c, int, double* out) { return cluster_error(c, out); }
-  bool may_free_run(const pmf_ctx*, int, double) const { return false; }
-  int enqueue(pmf_ctx* c, int, int, int, double) { return fail(c, PMF_EINVAL, "Kmeans / Cmeans: no free-running loop"); }
-  void rewind(pmf_ctx*, int, int) {}
-  int close(pmf_ctx*) { return PMF_OK; }
-};
 
 }  // namespace

@@ -166,7 +166,7 @@ struct pmf_ctx {
   double *dSvState = nullptr, *dSvPart = nullptr, *dSvScal = nullptr, *dSvLam = nullptr;
   int *dSvPartIdx = nullptr, *dSvSel = nullptr, *dSvSide = nullptr, *dSvUnf = nullptr;
   float* dSvF = nullptr;
-  int sv_wgs = 0, sv_ppw = 0;   // workgroups of k_sivm_pass, 64-column panels each owns
+  int sv_wgs = 0, sv_ppw = 0;   // AA: workgroups of k_aa_price, 64-column panels each owns (k_sivm_pass takes its partition per call)
   int sv_metric = 0;            // pmf_set_option("sivm_metric"): 0 l2, 1 l1, 2 cosine
   int sv_init = 0;              // pmf_set_option("sivm_init"): 0 fastmap, 1 origin
   bool sv_have_select = false;  // dSvSel holds the selection of a W step
@@ -347,18 +347,21 @@ int ensure_dv(pmf_ctx* c) {
 }
 
 // ---- profiling of the dominant kernel -------------------------------------------------
+// Does this launch of the profiled site carry events (every N-th does)?  If so, s.ev[s.used] and s.ev[s.used + 1] exist on return.
+bool stat_next_pair(KernelStat& s) {
+  if (s.seen++ % s.every != 0) return false;
+  while (s.used + 2 > s.ev.size()) {
+    hipEvent_t e;
+    if (hipEventCreate(&e) != hipSuccess) return false;
+    s.ev.push_back(e);
+  }
+  return true;
+}
 void stat_begin(pmf_ctx* c, int site) {
   if (!c->profile || c->stat.site != site) return;
   KernelStat& s = c->stat;
   s.open = false;
-  if (s.seen++ % s.every != 0) return;
-  if (s.used + 2 > s.ev.size()) {
-    for (int q = 0; q < 2; ++q) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) return;
-      s.ev.push_back(e);
-    }
-  }
+  if (!stat_next_pair(s)) return;
   (void)hipEventRecord(s.ev[s.used], c->stream);   // profiling aid: a failed record only loses a sample
   s.open = true;
 }
@@ -367,14 +370,7 @@ void stat_pair(pmf_ctx* c, int site, hipEvent_t* e0, hipEvent_t* e1) {
   *e0 = *e1 = nullptr;
   if (!c->profile || c->stat.site != site) return;
   KernelStat& s = c->stat;
-  if (s.seen++ % s.every != 0) return;
-  if (s.used + 2 > s.ev.size()) {
-    for (int q = 0; q < 2; ++q) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) return;
-      s.ev.push_back(e);
-    }
-  }
+  if (!stat_next_pair(s)) return;
   *e0 = s.ev[s.used]; *e1 = s.ev[s.used + 1];
   s.used += 2;
 }

@@ -10,26 +10,34 @@ int cur_check(pmf_ctx* c, const char* who) {
   return PMF_OK;
 }
 
-// cur.py:84-97 without the normalisation: the row sums (m) and column sums (n) of data^2 in float64, one read of V
-int cur_sqnorms(pmf_ctx* c, double* row_sq, double* col_sq) {
-  PMFCHK(cur_check(c, "pmf_cur_sqnorms"));
+// the row sums [mp] and, behind them, the column sums [np] of V^2 in float64, one read of V, into a temporary of the call;
+// timed: the launch is the one that SITE_CUR_SQNORMS brackets
+int sqnorms_f64(pmf_ctx* c, DevTemps& tmp, bool timed, double** sq) {
   const int64_t mp = c->mp, np = c->np;
   const int npanels = (int)((np + PMF_CUR_PANEL - 1) / PMF_CUR_PANEL), nblocks = (int)(mp / 64);
-  DevTemps tmp;
-  double *rowpart = nullptr, *colpart = nullptr, *out = nullptr;
+  double *rowpart = nullptr, *colpart = nullptr;
   PMFCHK(talloc(c, tmp, &rowpart, (size_t)npanels * mp));
   PMFCHK(talloc(c, tmp, &colpart, (size_t)nblocks * np));
-  PMFCHK(talloc(c, tmp, &out, (size_t)(mp + np)));
-  stat_begin(c, SITE_CUR_SQNORMS);
+  PMFCHK(talloc(c, tmp, sq, (size_t)(mp + np)));
+  if (timed) stat_begin(c, SITE_CUR_SQNORMS);
   hipLaunchKernelGGL(k_cur_sqnorms, dim3((unsigned)((int64_t)nblocks * npanels)), dim3(256), 0, c->stream, (const float*)c->dV, np, mp, npanels,
                      rowpart, colpart);
-  stat_end(c, SITE_CUR_SQNORMS);
+  if (timed) stat_end(c, SITE_CUR_SQNORMS);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_cur_sqnorms_reduce, dim3((unsigned)((mp + np) / 64)), dim3(1024), 0, c->stream, (const double*)rowpart, npanels, mp,
-                     (const double*)colpart, nblocks, np, out);
+                     (const double*)colpart, nblocks, np, *sq);
   HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
+// cur.py:84-97 without the normalisation: the row sums (m) and column sums (n) of data^2
+int cur_sqnorms(pmf_ctx* c, double* row_sq, double* col_sq) {
+  PMFCHK(cur_check(c, "pmf_cur_sqnorms"));
+  DevTemps tmp;
+  double* out = nullptr;
+  PMFCHK(sqnorms_f64(c, tmp, true, &out));
   if (row_sq) HIPCHK(c, hipMemcpyAsync(row_sq, out, (size_t)c->m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (col_sq) HIPCHK(c, hipMemcpyAsync(col_sq, out + mp, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (col_sq) HIPCHK(c, hipMemcpyAsync(col_sq, out + c->mp, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
   return PMF_OK;
 }

@@ -1,4 +1,4 @@
-// pmf_host_factorize.h -- NMF / BNMF / RNMF / SNMF / NMFALS and PCA: the steps that pmf_factorize hands to the loop (pmf_host_loop.h)
+// pmf_host_factorize.h -- NMF / BNMF / RNMF / SNMF / NMFALS: the steps that pmf_factorize hands to the loop (pmf_host_loop.h)
 // Host code of libpymf_hip.so: included by pmf_api.hip (the translation unit) in this order, nothing else includes it.
 #pragma once
 
@@ -139,21 +139,6 @@ NmfLoopSteps nmf_loop_steps(pmf_ctx* c, int niter, bool cw, bool ch, bool ce) {
                    !(c->host_ar && !(c->ipc.nranks > 1 && (size_t)ps_elems(c) * sizeof(float) <= PMF_IPC_MAX_BYTES));
   return s;
 }
-
-// pmf_factorize for PCA: one iteration (pca.py:110-135), no free-running form, the direct residual
-struct PcaLoopSteps {
-  bool cw, ch;
-  int iterate(pmf_ctx* c, int) {
-    if (cw) PMFCHK(pca_update_w(c));
-    if (ch) PMFCHK(pca_update_h(c));
-    return PMF_OK;
-  }
-  int error(pmf_ctx* c, int, double* out) { return pca_error(c, out); }
-  bool may_free_run(const pmf_ctx*, int, double) const { return false; }
-  int enqueue(pmf_ctx* c, int, int, int, double) { return fail(c, PMF_EINVAL, "PCA: no free-running loop"); }
-  void rewind(pmf_ctx*, int, int) {}
-  int close(pmf_ctx*) { return PMF_OK; }
-};
 
 // every early (error) return of pmf_factorize leaves no pipelined W = V M write in flight on the side stream: a caller that
 // then re-uploads W must not see the stale product land on top of it

@@ -113,30 +113,9 @@ int greedy_select(pmf_ctx* c, bool trans, int nsel, int* dsel) {
   // ---- the pass over column panels of A (R <= 2432 rows) -------------------------------------------------------------------
   const float* A = c->dV;
   int64_t ld = c->np;
-  if (trans) {                                         // the transposed view as a matrix of its own: [np][mp]
-    float* AT = nullptr;
-    PMFCHK(talloc(c, tmp, &AT, (size_t)c->np * c->mp));
-    hipLaunchKernelGGL(k_greedy_transpose, dim3((unsigned)(c->mp / 64), (unsigned)(c->np / 64)), dim3(256), 0, c->stream, (const float*)c->dV,
-                       (int64_t)c->np, AT, (int64_t)c->mp);
-    HIPCHK(c, hipGetLastError());
-    A = AT;
-    ld = c->mp;
-  }
-  // |v_j|^2 in float64: the row sums and column sums of V^2 (k_cur_sqnorms), whichever side the columns of A are
-  double *rowpart = nullptr, *colpart = nullptr, *sq = nullptr;
-  {
-    const int64_t mp = c->mp, np = c->np;
-    const int npanels = (int)((np + PMF_CUR_PANEL - 1) / PMF_CUR_PANEL), nblocks = (int)(mp / 64);
-    PMFCHK(talloc(c, tmp, &rowpart, (size_t)npanels * mp));
-    PMFCHK(talloc(c, tmp, &colpart, (size_t)nblocks * np));
-    PMFCHK(talloc(c, tmp, &sq, (size_t)(mp + np)));
-    hipLaunchKernelGGL(k_cur_sqnorms, dim3((unsigned)((int64_t)nblocks * npanels)), dim3(256), 0, c->stream, (const float*)c->dV, np, mp, npanels,
-                       rowpart, colpart);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_cur_sqnorms_reduce, dim3((unsigned)((mp + np) / 64)), dim3(1024), 0, c->stream, (const double*)rowpart, npanels, mp,
-                       (const double*)colpart, nblocks, np, sq);
-    HIPCHK(c, hipGetLastError());
-  }
+  if (trans) PMFCHK(transposed_view(c, tmp, &A, &ld));
+  double* sq = nullptr;                                // |v_j|^2 in float64: the row sums or the column sums of V^2, whichever side the columns of A are
+  PMFCHK(sqnorms_f64(c, tmp, false, &sq));
   const double* nrm2 = trans ? sq : sq + c->mp;
   double *Bp = nullptr, *Q = nullptr, *pscore = nullptr;
   float* Op = nullptr;
@@ -151,8 +130,8 @@ int greedy_select(pmf_ctx* c, bool trans, int nsel, int* dsel) {
                      (const int*)order, (const double*)dsv, cc, R, Rp, 1, Bp, Op, op_elems, (const double*)nullptr, (double*)nullptr, taken, Cp);
   HIPCHK(c, hipGetLastError());
   const int npanels = Cp / 64;
-  const int ppw = (npanels + std::min(npanels, PMF_CL_MAX_WGS) - 1) / std::min(npanels, PMF_CL_MAX_WGS);
-  const int wgs = (npanels + ppw - 1) / ppw;
+  int ppw = 0, wgs = 0;
+  panel_partition(npanels, PMF_CL_MAX_WGS, &ppw, &wgs);
   GreedyPassArgs p{};
   p.A = A; p.Op = Op; p.nrm2 = nrm2; p.taken = taken; p.pscore = pscore; p.pidx = pidx; p.ld = ld; p.m = R; p.n = C; p.c = cc;
   p.npanels = npanels; p.panels_per_wg = ppw;
@@ -185,13 +164,7 @@ int greedy_select_host(pmf_ctx* c, bool trans, int nsel, int32_t* select) {
 int greedy_update_w(pmf_ctx* c) {
   if (!c->dSvSel) PMFCHK(dalloc(c, &c->dSvSel, (size_t)c->KP));
   PMFCHK(greedy_select(c, false, c->k, c->dSvSel));
-  const int64_t elems = c->mp * c->KP;
-  hipLaunchKernelGGL(k_sivm_gather, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->dV, (int64_t)c->np,
-                     (int)c->m, (int)c->n, c->k, c->KP, elems, (const int*)c->dSvSel, c->dW);
-  HIPCHK(c, hipGetLastError());
-  w_replaced(c, false);
-  c->sv_have_select = true;
-  return PMF_OK;
+  return gather_selected_w(c);
 }
 
 // GREEDY.update_h (greedy.py:82-86): H = pinv(W) data, pinv(W) = (W^T W)^+ W^T with svd.py's 1e-8 cut on the eigenvalues (float64
@@ -231,27 +204,5 @@ int greedy_update_h(pmf_ctx* c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
   return PMF_OK;
 }
-
-// pmf_factorize for GREEDY: NMF.factorize's loop (nmf.py:182-202).  Both steps depend on the data alone (update_w) or on the data
-// and W (update_h) and give the same bits every time, so the iterations behind the first repeat its result without running again.
-struct GreedyLoopSteps {
-  bool cw, ch;
-  double f0 = 0.0;
-  int iterate(pmf_ctx* c, int i) {
-    if (i > 0) return PMF_OK;
-    if (cw) PMFCHK(greedy_update_w(c));
-    if (ch) PMFCHK(greedy_update_h(c));
-    return PMF_OK;
-  }
-  int error(pmf_ctx* c, int i, double* out) {
-    if (i == 0) PMFCHK(frobenius_direct(c, &f0));
-    *out = f0;
-    return PMF_OK;
-  }
-  bool may_free_run(const pmf_ctx*, int, double) const { return false; }
-  int enqueue(pmf_ctx* c, int, int, int, double) { return fail(c, PMF_EINVAL, "GREEDY: no free-running loop"); }
-  void rewind(pmf_ctx*, int, int) {}
-  int close(pmf_ctx*) { return PMF_OK; }
-};
 
 }  // namespace

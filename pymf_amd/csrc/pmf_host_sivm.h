@@ -11,18 +11,8 @@ constexpr int PMF_SIVM_ROUND_CAP = 48;
 constexpr int PMF_SIVM_BLIND_ROUNDS = 8;
 constexpr double PMF_SIVM_SUM_TOL = 1e-6;   // |sum x - 1|: eight units in the last place of a float32 one
 
-// contiguous ranges of 64-column panels over at most PMF_CL_MAX_WGS workgroups (the partition of cluster_alloc, without its
-// slab limit): k_sivm_pass and k_aa_price
-void panel_partition(pmf_ctx* c) {
-  const int npanels = c->np / 64;
-  const int want = std::min(npanels, PMF_CL_MAX_WGS);
-  c->sv_ppw = (npanels + want - 1) / want;
-  c->sv_wgs = (npanels + c->sv_ppw - 1) / c->sv_ppw;
-}
-
 int sivm_alloc(pmf_ctx* c) {
   if (c->dSvState) return PMF_OK;
-  panel_partition(c);
   PMFCHK(dalloc(c, &c->dSvState, (size_t)3 * c->np));
   PMFCHK(dalloc(c, &c->dSvPart, (size_t)2 * PMF_CL_MAX_WGS));
   PMFCHK(dalloc(c, &c->dSvPartIdx, (size_t)2 * PMF_CL_MAX_WGS));
@@ -46,48 +36,6 @@ int sivm_launch_pass(pmf_ctx* c, const SivmArgs& a, int wgs, int metric) {
   return PMF_OK;
 }
 
-// SIVM.update_w (sivm.py:145-201): num_bases + 2 ('fastmap') or num_bases ('origin') launches back to back, the closing
-// reduce and the gather; nothing is read by the host in between
-int sivm_update_w(pmf_ctx* c) {
-  PMFCHK(sivm_alloc(c));
-  HIPCHK(c, hipMemsetAsync(c->dSvState, 0, (size_t)3 * c->np * sizeof(double), c->stream));
-  const bool origin = c->sv_init == 1;
-  SivmArgs a{};
-  a.V = c->dV;
-  a.dij = c->dSvState; a.dsum = c->dSvState + c->np; a.dsq = c->dSvState + 2 * (int64_t)c->np;
-  a.select = c->dSvSel; a.scal = c->dSvScal;
-  a.np = c->np; a.m = (int)c->m; a.n = (int)c->n;
-  a.npanels = c->np / 64; a.panels_per_wg = c->sv_ppw;
-  a.fixed_idx = origin ? -1 : 0;
-  int pass = 0;
-  auto run = [&](int nprev, int use_fixed, int sel_pos, int take_maxd, int plain, int l) -> int {
-    const int out = pass & 1, in = out ^ 1;
-    a.pscore_in = c->dSvPart + in * PMF_CL_MAX_WGS; a.pidx_in = c->dSvPartIdx + in * PMF_CL_MAX_WGS;
-    a.pscore_out = c->dSvPart + out * PMF_CL_MAX_WGS; a.pidx_out = c->dSvPartIdx + out * PMF_CL_MAX_WGS;
-    a.nprev = nprev; a.use_fixed = use_fixed; a.sel_pos = sel_pos; a.take_maxd = take_maxd; a.plain = plain; a.l = l;
-    ++pass;
-    return sivm_launch_pass(c, a, c->sv_wgs, c->sv_metric);
-  };
-  // sivm.py:145-166: three distance passes from column 0 ('fastmap'), or one from the origin
-  const int nplain = origin ? 1 : 3;
-  for (int p = 0; p < nplain; ++p) PMFCHK(run(p == 0 ? 0 : c->sv_wgs, p == 0, -1, 0, 1, 0));
-  // sivm.py:181-193: pass l measures against select[l - 1] (the first: the last plain pass's argmax, or -1) and finds select[l]
-  for (int l = 1; l < c->k; ++l) PMFCHK(run(c->sv_wgs, origin && l == 1, l - 1, l == 1, 0, l));
-  const int last = (pass - 1) & 1;
-  hipLaunchKernelGGL(k_sivm_close, dim3(1), dim3(256), 0, c->stream, (const double*)(c->dSvPart + last * PMF_CL_MAX_WGS),
-                     (const int*)(c->dSvPartIdx + last * PMF_CL_MAX_WGS), c->sv_wgs, (int)c->n, c->k - 1, c->k == 1 ? 1 : 0,
-                     (origin && c->k == 1) ? 1 : 0, c->dSvSel, c->dSvScal);
-  HIPCHK(c, hipGetLastError());
-  const int64_t elems = c->mp * c->KP;
-  hipLaunchKernelGGL(k_sivm_gather, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->dV, (int64_t)c->np,
-                     (int)c->m, (int)c->n, c->k, c->KP, elems, (const int*)c->dSvSel, c->dW);
-  HIPCHK(c, hipGetLastError());
-  w_replaced(c, false);
-  c->sv_have_select = true;
-  return PMF_OK;
-}
-
-// ---- pmf_sivm_select: the selection alone, among the columns of the resident V or among its rows (SIVM_CUR) --------------------
 // The rounds of update_w (sivm.py:145-201) as (plain, l, take_maxd, keep, sel_pos, last) per round: three plain rounds from
 // candidate 0 ('fastmap') or one from the origin, then round l measures against select[l - 1] and finds select[l].
 struct SivmRound { int plain, l, take_maxd, keep, sel_pos, last; };
@@ -101,41 +49,69 @@ std::vector<SivmRound> sivm_rounds(int nsel, bool origin) {
   return r;
 }
 
-// k_sivm_pass on A [R rows][ld], candidates its C columns; state and partials are temporaries of the call
-int sivm_select_panels(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, int* dsel, DevTemps& tmp) {
-  const int npanels = (int)(ld / 64);
-  const int want = std::min(npanels, PMF_CL_MAX_WGS);
-  const int ppw = (npanels + want - 1) / want, wgs = (npanels + ppw - 1) / ppw;
-  double *state = nullptr, *part = nullptr, *scal = nullptr;
-  int* pidx = nullptr;
-  PMFCHK(talloc(c, tmp, &state, (size_t)3 * ld));
-  PMFCHK(talloc(c, tmp, &part, (size_t)2 * PMF_CL_MAX_WGS));
-  PMFCHK(talloc(c, tmp, &pidx, (size_t)2 * PMF_CL_MAX_WGS));
-  PMFCHK(talloc(c, tmp, &scal, 2));
-  HIPCHK(c, hipMemsetAsync(state, 0, (size_t)3 * ld * sizeof(double), c->stream));
+// what the column-panel rounds write: the recurrence's state [3][ld], the two partials arrays of the argmax ([2][PMF_CL_MAX_WGS]
+// each), (maxd, a) and the selection -- the resident buffers of the context (update_w) or temporaries of a pmf_sivm_select call
+struct SivmBufs { double* state; double* part; int* pidx; double* scal; int* select; };
+
+// k_sivm_pass on A [R rows][ld], candidates its C columns: nsel + 2 ('fastmap') or nsel ('origin') launches back to back and the
+// closing reduce; a round's argmax is taken in the next launch's prologue, nothing is read by the host in between
+int sivm_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, const SivmBufs& b) {
+  int ppw = 0, wgs = 0;
+  panel_partition((int)(ld / 64), PMF_CL_MAX_WGS, &ppw, &wgs);
+  HIPCHK(c, hipMemsetAsync(b.state, 0, (size_t)3 * ld * sizeof(double), c->stream));
   SivmArgs a{};
   a.V = A;
-  a.dij = state; a.dsum = state + ld; a.dsq = state + 2 * ld;
-  a.select = dsel; a.scal = scal;
+  a.dij = b.state; a.dsum = b.state + ld; a.dsq = b.state + 2 * ld;
+  a.select = b.select; a.scal = b.scal;
   a.np = ld; a.m = R; a.n = C;
-  a.npanels = npanels; a.panels_per_wg = ppw;
+  a.npanels = (int)(ld / 64); a.panels_per_wg = ppw;
   a.fixed_idx = origin ? -1 : 0;
   const std::vector<SivmRound> rounds = sivm_rounds(nsel, origin);
-  for (size_t p = 0; p < rounds.size(); ++p) {         // as sivm_update_w: a round's argmax is taken in the next launch's prologue
+  for (size_t p = 0; p < rounds.size(); ++p) {
     const SivmRound& r = rounds[p];
     const int out = (int)(p & 1), in = out ^ 1;
-    a.pscore_in = part + in * PMF_CL_MAX_WGS; a.pidx_in = pidx + in * PMF_CL_MAX_WGS;
-    a.pscore_out = part + out * PMF_CL_MAX_WGS; a.pidx_out = pidx + out * PMF_CL_MAX_WGS;
+    a.pscore_in = b.part + in * PMF_CL_MAX_WGS; a.pidx_in = b.pidx + in * PMF_CL_MAX_WGS;
+    a.pscore_out = b.part + out * PMF_CL_MAX_WGS; a.pidx_out = b.pidx + out * PMF_CL_MAX_WGS;
     a.nprev = p == 0 ? 0 : wgs;
     a.use_fixed = p == 0 || (origin && r.l == 1);
     a.sel_pos = r.sel_pos; a.take_maxd = r.l == 1; a.plain = r.plain; a.l = r.l;
     PMFCHK(sivm_launch_pass(c, a, wgs, metric));
   }
   const int last = (int)((rounds.size() - 1) & 1);
-  hipLaunchKernelGGL(k_sivm_close, dim3(1), dim3(256), 0, c->stream, (const double*)(part + last * PMF_CL_MAX_WGS),
-                     (const int*)(pidx + last * PMF_CL_MAX_WGS), wgs, C, nsel - 1, nsel == 1 ? 1 : 0, (origin && nsel == 1) ? 1 : 0, dsel, scal);
+  hipLaunchKernelGGL(k_sivm_close, dim3(1), dim3(256), 0, c->stream, (const double*)(b.part + last * PMF_CL_MAX_WGS),
+                     (const int*)(b.pidx + last * PMF_CL_MAX_WGS), wgs, C, nsel - 1, nsel == 1 ? 1 : 0, (origin && nsel == 1) ? 1 : 0, b.select, b.scal);
   HIPCHK(c, hipGetLastError());
   return PMF_OK;
+}
+
+// W = V[:, select] for the selection in dSvSel (SIVM, GREEDY)
+int gather_selected_w(pmf_ctx* c) {
+  const int64_t elems = c->mp * c->KP;
+  hipLaunchKernelGGL(k_sivm_gather, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->dV, (int64_t)c->np,
+                     (int)c->m, (int)c->n, c->k, c->KP, elems, (const int*)c->dSvSel, c->dW);
+  HIPCHK(c, hipGetLastError());
+  w_replaced(c, false);
+  c->sv_have_select = true;
+  return PMF_OK;
+}
+
+// SIVM.update_w (sivm.py:145-201): the rounds on the resident V and buffers, then the gather
+int sivm_update_w(pmf_ctx* c) {
+  PMFCHK(sivm_alloc(c));
+  PMFCHK(sivm_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_metric, c->sv_init == 1,
+                           SivmBufs{c->dSvState, c->dSvPart, c->dSvPartIdx, c->dSvScal, c->dSvSel}));
+  return gather_selected_w(c);
+}
+
+// ---- pmf_sivm_select: the selection alone, among the columns of the resident V or among its rows (SIVM_CUR) --------------------
+// the column-panel rounds with state and partials as temporaries of the call
+int sivm_select_panels(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, int* dsel, DevTemps& tmp) {
+  SivmBufs b{nullptr, nullptr, nullptr, nullptr, dsel};
+  PMFCHK(talloc(c, tmp, &b.state, (size_t)3 * ld));
+  PMFCHK(talloc(c, tmp, &b.part, (size_t)2 * PMF_CL_MAX_WGS));
+  PMFCHK(talloc(c, tmp, &b.pidx, (size_t)2 * PMF_CL_MAX_WGS));
+  PMFCHK(talloc(c, tmp, &b.scal, 2));
+  return sivm_panel_rounds(c, A, ld, R, C, nsel, metric, origin, b);
 }
 
 template <int METRIC>
@@ -197,21 +173,25 @@ bool sivm_rows_path(const pmf_ctx* c, bool trans, int path) {
   return path == 0 ? (trans == (c->m <= PMF_SIVM_MAX_M)) : path == 2;
 }
 
+// the transposed view of the resident V as a matrix of its own, [np][mp], a temporary of the call
+int transposed_view(pmf_ctx* c, DevTemps& tmp, const float** A, int64_t* ld) {
+  float* AT = nullptr;
+  PMFCHK(talloc(c, tmp, &AT, (size_t)c->np * c->mp));
+  hipLaunchKernelGGL(k_greedy_transpose, dim3((unsigned)(c->mp / 64), (unsigned)(c->np / 64)), dim3(256), 0, c->stream, (const float*)c->dV,
+                     (int64_t)c->np, AT, (int64_t)c->mp);
+  HIPCHK(c, hipGetLastError());
+  *A = AT;
+  *ld = c->mp;
+  return PMF_OK;
+}
+
 int sivm_select(pmf_ctx* c, bool trans, int nsel, int metric, bool origin, int path, int* dsel) {
   const int64_t C = trans ? c->m : c->n, R = trans ? c->n : c->m;
   const bool rows_path = sivm_rows_path(c, trans, path);
   DevTemps tmp;
   const float* A = c->dV;
   int64_t ld = c->np;
-  if (rows_path != trans) {                            // the pass wants the other layout: the transposed view as a matrix of its own, [np][mp]
-    float* AT = nullptr;
-    PMFCHK(talloc(c, tmp, &AT, (size_t)c->np * c->mp));
-    hipLaunchKernelGGL(k_greedy_transpose, dim3((unsigned)(c->mp / 64), (unsigned)(c->np / 64)), dim3(256), 0, c->stream, (const float*)c->dV,
-                       (int64_t)c->np, AT, (int64_t)c->mp);
-    HIPCHK(c, hipGetLastError());
-    A = AT;
-    ld = c->mp;
-  }
+  if (rows_path != trans) PMFCHK(transposed_view(c, tmp, &A, &ld));   // the pass wants the other layout
   if (rows_path) PMFCHK(sivm_select_rows(c, A, ld, (int)C, (int)R, nsel, metric, origin, dsel, tmp));
   else PMFCHK(sivm_select_panels(c, A, ld, (int)R, (int)C, nsel, metric, origin, dsel, tmp));
   HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
@@ -285,20 +265,5 @@ int sivm_update_h(pmf_ctx* c) {
                                  std::to_string(PMF_SIVM_ROUND_CAP) + " rounds");
   return PMF_OK;
 }
-
-// pmf_factorize for SIVM: one iteration (sivm.py:203-228), no free-running form, the direct residual
-struct SivmLoopSteps {
-  bool cw, ch;
-  int iterate(pmf_ctx* c, int) {
-    if (cw) PMFCHK(sivm_update_w(c));
-    if (ch) PMFCHK(sivm_update_h(c));
-    return PMF_OK;
-  }
-  int error(pmf_ctx* c, int, double* out) { return frobenius_direct(c, out); }
-  bool may_free_run(const pmf_ctx*, int, double) const { return false; }
-  int enqueue(pmf_ctx* c, int, int, int, double) { return fail(c, PMF_EINVAL, "SIVM: no free-running loop"); }
-  void rewind(pmf_ctx*, int, int) {}
-  int close(pmf_ctx*) { return PMF_OK; }
-};
 
 }  // namespace
