@@ -38,6 +38,7 @@
  *   pmf_set/get_g_f64     self.G of CNMF               pymf/cnmf.py:95-100
  *   pmf_cluster_get/set_assigned  self.assigned of Kmeans  pymf/kmeans.py:77 (algo 6)
  *   pmf_sivm_get_select   self.select of SIVM          pymf/sivm.py:145-166,193 (algo 10)
+ *   pmf_update_w under "sivm_rule" 1 / 2  LAESA.update_w / GMAP.update_w  pymf/laesa.py:63-82 / pymf/gmap.py:119-165 (algo 10)
  *   pmf_sivm_select       SIVM_CUR.sample              pymf/sivm_cur.py:65-73 (algo 10 or 14)
  *   pmf_svd_decompose / pmf_svd_get  SVD.factorize, U / S / V  pymf/svd.py:110-158 (algo 12; PCA: pymf/pca.py)
  *   pmf_cur_sqnorms       CUR.sample_probability       pymf/cur.py:84-97 (algo 14)
@@ -239,7 +240,22 @@ int pmf_cluster_set_assigned(pmf_ctx* ctx, const int32_t* assigned);
  *   pmf_factorize    update_w, update_h, ||V - W H|| under the PMF_COMPUTE_* flags; the class always passes niter = 1
  *   pmf_frobenius    the direct residual
  * pmf_sivm_get_select: the num_bases selected column indices of the last pmf_update_w in selection order; under 'origin' the
- * first is -1, which W treats as a Python index (the LAST data column, sivm.py:198).  GREEDY contexts (algo 15) answer it too. */
+ * first is -1, which W treats as a Python index (the LAST data column, sivm.py:198).  GREEDY contexts (algo 15) answer it too.
+ *
+ * LAESA and GMAP run on the same context (no algorithm number of their own): pmf_set_option "sivm_rule" (0 SIVM default,
+ * 1 LAESA, 2 GMAP) chooses the rule pmf_update_w selects by, "gmap_method" (0 'pca' default, 1 'aa', 2 'nmf') GMAP's method;
+ * both options are refused (PMF_EINVAL) on other contexts and out of range.  Limits, pmf_update_h, pmf_factorize,
+ * pmf_frobenius and pmf_sivm_get_select are SIVM's.
+ *   sivm_rule 1      LAESA.update_w (pymf/laesa.py:63-82): the plain rounds of 'fastmap' / 'origin' as above, then num_bases - 1
+ *                    rounds dmin = min(dmin, distance to the last selected column), select the argmax of dmin ("sivm_metric"
+ *                    and "sivm_init" apply): num_bases + 2 / num_bases launches of k_laesa_pass (pmf_colsel.h).  Distances
+ *                    fp32, dmin float64.
+ *   sivm_rule 2      GMAP.update_w (pymf/gmap.py:119-165 with robust_map = False): round 0 the column norms and the first
+ *                    argmax, then num_bases - 1 rounds c = v . x / (|v| |x|), iterval *= (1 - |c|) |v| ('pca'),
+ *                    ((1 - c) / 2) |v| ('aa') or 1 - |c| ('nmf'), select the argmax of iterval: num_bases launches of
+ *                    k_gmap_pass.  Sums of squares and dots fp32, norms and iterval float64.  A zero-norm column scores NaN
+ *                    and is never selected (the reference's np.argmax would pick it).  The robust_map = True path of the
+ *                    reference (a nested, randomly initialised Kmeans) is not provided. */
 int pmf_sivm_get_select(pmf_ctx* ctx, int32_t* select);
 
 /* pmf_sivm_select: SIVM's selection alone (pymf/sivm_cur.py:65-73: what SIVM_CUR.sample asks of SIVM) on a SIVM or a CUR / CMD
@@ -252,6 +268,7 @@ int pmf_sivm_get_select(pmf_ctx* ctx, int32_t* select);
  * at most 16384 candidates) does not allow it.  All rounds are enqueued back to back; state and partials are temporaries of
  * the call: the context's own selection state, pmf_update_w and pmf_sivm_get_select are not touched.  Dense resident data, one
  * rank, 1 <= nsel <= 64, min(rows, cols) <= 16384 -- PMF_EINVAL otherwise.  Two calls give the same bits.
+ * The rule is always SIVM's, whatever "sivm_rule" the context carries: SIVM_CUR depends on it.
  * pmf_set_option "profile_sivm_rows" (0 default, 1) makes pmf_profile_enable time the rounds of the long-sample pass. */
 int pmf_sivm_select(pmf_ctx* ctx, int32_t transposed, int32_t nsel, int32_t metric, int32_t init, int32_t path, int32_t* select);
 

@@ -23,7 +23,9 @@ from .cursl import CURSL      # noqa: F401  
 from .greedy import GREEDY    # noqa: F401  
 from .greedycur import GREEDYCUR   # noqa: F401  
 from .sivm_cur import SIVM_CUR     # noqa: F401  
+from .laesa import LAESA      # noqa: F401  
+from .gmap import GMAP        # noqa: F401  
 from . import dist            # noqa: F401
 
-__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "SVD", "PCA", "CUR", "CMD", "CURSL", "GREEDY", "GREEDYCUR", "SIVM_CUR", "pinv", "dist"]
+__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "SVD", "PCA", "CUR", "CMD", "CURSL", "GREEDY", "GREEDYCUR", "SIVM_CUR", "LAESA", "GMAP", "pinv", "dist"]
 __version__ = "0.1.0"

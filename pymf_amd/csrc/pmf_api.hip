@@ -37,6 +37,7 @@
 #include "pmf_cnmf.h"
 #include "pmf_cluster.h"
 #include "pmf_sivm.h"
+#include "pmf_colsel.h"
 #include "pmf_aa.h"
 #include "pmf_svd.h"
 #include "pmf_cur.h"
@@ -57,6 +58,7 @@
 #include "pmf_host_cnmf.h"
 #include "pmf_host_cluster.h"
 #include "pmf_host_sivm.h"
+#include "pmf_host_colsel.h"
 #include "pmf_host_aa.h"
 #include "pmf_host_svd.h"
 #include "pmf_host_cur.h"
@@ -1158,6 +1160,18 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
       if (value != 0 && value != 1) return fail(c, PMF_EINVAL, "sivm_init: 0 (fastmap) or 1 (origin)");
       c->sv_init = (int)value;
     }
+    return PMF_OK;
+  }
+  if (std::strcmp(name, "sivm_rule") == 0 || std::strcmp(name, "gmap_method") == 0) {
+    if (c->algo != PMF_ALGO_SIVM) return fail(c, PMF_EINVAL, "sivm_rule / gmap_method: SIVM contexts only");
+    if (name[0] == 's') {
+      if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "sivm_rule: 0 (SIVM), 1 (LAESA) or 2 (GMAP)");
+      c->sv_rule = (int)value;
+    } else {
+      if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "gmap_method: 0 (pca), 1 (aa) or 2 (nmf)");
+      c->sv_gmap_method = (int)value;
+    }
+    choose_stat_site(c, false);
     return PMF_OK;
   }
   if (std::strcmp(name, "profile_sivm_rows") == 0) {

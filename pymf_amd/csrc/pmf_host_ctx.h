@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_SIVM_ROWS, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY, SITE_CUR_LEV, SITE_CUR_SQNORMS };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_SIVM_ROWS, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY, SITE_CUR_LEV, SITE_CUR_SQNORMS, SITE_LAESA, SITE_GMAP };
 
 struct KernelStat {
   std::string name = "none";
@@ -169,6 +169,8 @@ struct pmf_ctx {
   int sv_wgs = 0, sv_ppw = 0;   // AA: workgroups of k_aa_price, 64-column panels each owns (k_sivm_pass takes its partition per call)
   int sv_metric = 0;            // pmf_set_option("sivm_metric"): 0 l2, 1 l1, 2 cosine
   int sv_init = 0;              // pmf_set_option("sivm_init"): 0 fastmap, 1 origin
+  int sv_rule = 0;              // pmf_set_option("sivm_rule"): 0 SIVM, 1 LAESA, 2 GMAP (pmf_colsel.h) -- what pmf_update_w selects by
+  int sv_gmap_method = 0;       // pmf_set_option("gmap_method"): 0 pca, 1 aa, 2 nmf
   bool sv_have_select = false;  // dSvSel holds the selection of a W step
   int opt_profile_sivm_rows = 0;   // pmf_set_option("profile_sivm_rows"): pmf_profile_enable times the rounds of the long-sample pass (SITE_SIVM_ROWS)
   // AA (pmf_aa.h): W_hat, the points X and residuals R ([mp][KP]); the two partials arrays of the pricing pass ([2][wgs][KP]); per

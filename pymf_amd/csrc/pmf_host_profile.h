@@ -24,6 +24,18 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.name = buf;
     st.flops = st.exec_flops = 4.0 * m * n * k;                  // W^T V and V H^T
     st.bytes = 4.0 * (m * n + k * n + 2.0 * m * k);              // V once, H written, W read, the sums written
+  } else if (c->algo == PMF_ALGO_SIVM && c->sv_rule == 1) {
+    st.site = SITE_LAESA;
+    snprintf(buf, sizeof(buf), "k_laesa_pass<%s>", c->sv_metric == 0 ? "l2" : c->sv_metric == 1 ? "l1" : "cosine");
+    st.name = buf;
+    st.flops = st.exec_flops = 3.0 * m * n;                       // difference, square, sum
+    st.bytes = 4.0 * m * (double)c->np + 16.0 * (double)c->np;   // V once; one float64 state array read and written
+  } else if (c->algo == PMF_ALGO_SIVM && c->sv_rule == 2) {
+    st.site = SITE_GMAP;
+    snprintf(buf, sizeof(buf), "k_gmap_pass<%s>", c->sv_gmap_method == 0 ? "pca" : c->sv_gmap_method == 1 ? "aa" : "nmf");
+    st.name = buf;
+    st.flops = st.exec_flops = 2.0 * m * n;                       // product, sum
+    st.bytes = 4.0 * m * (double)c->np + 24.0 * (double)c->np;   // (rounds >= 1) V once; the norms read, iterval read and written
   } else if (c->algo == PMF_ALGO_SIVM) {
     st.site = SITE_SIVM;
     snprintf(buf, sizeof(buf), "k_sivm_pass<%s>", c->sv_metric == 0 ? "l2" : c->sv_metric == 1 ? "l1" : "cosine");

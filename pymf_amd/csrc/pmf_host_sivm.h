@@ -95,11 +95,18 @@ int gather_selected_w(pmf_ctx* c) {
   return PMF_OK;
 }
 
-// SIVM.update_w (sivm.py:145-201): the rounds on the resident V and buffers, then the gather
+// the round drivers of the other two rules of a SIVM context (pmf_host_colsel.h)
+int laesa_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, const SivmBufs& b);
+int gmap_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int method, const SivmBufs& b);
+
+// SIVM.update_w (sivm.py:145-201), LAESA.update_w (laesa.py:63-82) or GMAP.update_w (gmap.py:119-165) by the context's rule:
+// the rounds on the resident V and buffers, then the gather
 int sivm_update_w(pmf_ctx* c) {
   PMFCHK(sivm_alloc(c));
-  PMFCHK(sivm_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_metric, c->sv_init == 1,
-                           SivmBufs{c->dSvState, c->dSvPart, c->dSvPartIdx, c->dSvScal, c->dSvSel}));
+  const SivmBufs b{c->dSvState, c->dSvPart, c->dSvPartIdx, c->dSvScal, c->dSvSel};
+  if (c->sv_rule == 1) PMFCHK(laesa_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_metric, c->sv_init == 1, b));
+  else if (c->sv_rule == 2) PMFCHK(gmap_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_gmap_method, b));
+  else PMFCHK(sivm_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_metric, c->sv_init == 1, b));
   return gather_selected_w(c);
 }
 
@@ -168,7 +175,7 @@ int sivm_select_rows(pmf_ctx* c, const float* A, int64_t ld, int C, int R, int n
 
 // nsel indices in selection order into dsel (device): among the columns of V, or (trans) among its rows.  path 0: by shape
 // (DESIGN.md 3.17); 1 / 2: k_sivm_pass / the long-sample pass forced, on a transposed copy where the layout needs one.
-// Synchronises at the end.
+// Synchronises at the end.  Always SIVM's rule, whatever "sivm_rule" the context carries (SIVM_CUR depends on it).
 bool sivm_rows_path(const pmf_ctx* c, bool trans, int path) {
   return path == 0 ? (trans == (c->m <= PMF_SIVM_MAX_M)) : path == 2;
 }
