@@ -255,8 +255,23 @@ int pmf_cluster_set_assigned(pmf_ctx* ctx, const int32_t* assigned);
  *                    ((1 - c) / 2) |v| ('aa') or 1 - |c| ('nmf'), select the argmax of iterval: num_bases launches of
  *                    k_gmap_pass.  Sums of squares and dots fp32, norms and iterval float64.  A zero-norm column scores NaN
  *                    and is never selected (the reference's np.argmax would pick it).  The robust_map = True path of the
- *                    reference (a nested, randomly initialised Kmeans) is not provided. */
+ *                    reference (a nested, randomly initialised Kmeans) is not provided.
+ *
+ * SIVM_SGREEDY (pymf/sivm_sgreedy.py:96-133, the exact greedy max-volume selection) runs on the same context under
+ * pmf_set_option "sivm_sgreedy" (0 default, 1); the option is refused (PMF_EINVAL) on other contexts, out of range and together
+ * with "sivm_rule" 1 or 2.  pmf_update_w then runs init_sivm's plain rounds ("sivm_metric" and "sivm_init" apply to them alone:
+ * three launches of k_laesa_pass for 'fastmap', one for 'origin') and num_bases - 1 rounds of k_sgreedy_step and k_sgreedy_pass
+ * (pmf_sgreedy.h): the Cayley-Menger volume of "selected + candidate" for every column from l2 distances, as
+ * det(CM_S) (-b^T inv(CM_S) b) with the squared distances fp32 and everything behind them float64; the argmax joins the
+ * selection.  pmf_sivm_get_select answers in the reference's order of `select` -- all but the last pick ascending, then the last
+ * pick; under 'origin' the first entry is -1: the last data column is the first vertex -- and W's columns follow it.  Selections
+ * are the reference's while the selected columns stay affinely independent (num_bases <= data_dimension + 1 on data in general
+ * position); beyond that every volume is rounding noise in the reference too, and the indices returned are valid but arbitrary.
+ * pmf_sivm_select keeps SIVM's rule on such a context.  Limits, pmf_update_h, pmf_factorize and pmf_frobenius are SIVM's.
+ * pmf_sivm_get_volumes: the num_bases - 1 volumes of the rounds of the last pmf_update_w (the reference's _v), float64;
+ * contexts under "sivm_sgreedy" only. */
 int pmf_sivm_get_select(pmf_ctx* ctx, int32_t* select);
+int pmf_sivm_get_volumes(pmf_ctx* ctx, double* volumes);
 
 /* pmf_sivm_select: SIVM's selection alone (pymf/sivm_cur.py:65-73: what SIVM_CUR.sample asks of SIVM) on a SIVM or a CUR / CMD
  * context -- nsel indices in selection order among the columns of V (transposed = 0) or among its rows (transposed = 1: SIVM on

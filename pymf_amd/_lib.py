@@ -68,6 +68,7 @@ SYMBOLS = [
     ("pmf_cluster_get_assigned", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_cluster_set_assigned", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_sivm_get_select", _c.c_int, [_ctx, _c.c_void_p]),
+    ("pmf_sivm_get_volumes", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_greedy_select", _c.c_int, [_ctx, _c.c_int32, _c.c_int32, _c.c_void_p]),
     ("pmf_sivm_select", _c.c_int, [_ctx, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p]),
     ("pmf_aa_get_beta", _c.c_int, [_ctx, _c.c_void_p]),
@@ -390,6 +391,12 @@ class Context(object):
         out = np.empty(self.k, dtype=np.int32)
         self._chk(self._lib.pmf_sivm_get_select(self._h, out.ctypes.data))
         return out
+
+    def get_volumes(self):
+        """SIVM_SGREEDY: the num_bases - 1 volumes of the rounds of the last update_w, float64 (pmf_sivm_get_volumes)."""
+        out = np.empty(max(self.k - 1, 1), dtype=np.float64)
+        self._chk(self._lib.pmf_sivm_get_volumes(self._h, out.ctypes.data))
+        return out[:self.k - 1]
 
     def greedy_select(self, nsel, transposed=False):
         """GREEDY / GREEDYCUR: `nsel` indices in selection order among the columns of the data, or (transposed) among its rows

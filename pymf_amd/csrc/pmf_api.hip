@@ -38,6 +38,7 @@
 #include "pmf_cluster.h"
 #include "pmf_sivm.h"
 #include "pmf_colsel.h"
+#include "pmf_sgreedy.h"
 #include "pmf_aa.h"
 #include "pmf_svd.h"
 #include "pmf_cur.h"
@@ -59,6 +60,7 @@
 #include "pmf_host_cluster.h"
 #include "pmf_host_sivm.h"
 #include "pmf_host_colsel.h"
+#include "pmf_host_sgreedy.h"
 #include "pmf_host_aa.h"
 #include "pmf_host_svd.h"
 #include "pmf_host_cur.h"
@@ -501,6 +503,14 @@ int pmf_sivm_get_select(pmf_ctx* c, int32_t* select) {
   HIPCHK(c, hipMemcpyAsync(select, c->dSvSel, (size_t)c->k * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return PMF_OK;
+}
+
+int pmf_sivm_get_volumes(pmf_ctx* c, double* volumes) {
+  if (!c || !volumes) return fail(c, PMF_EINVAL, "pmf_sivm_get_volumes: bad arguments");
+  if (c->algo != PMF_ALGO_SIVM || !c->sv_sgreedy) return fail(c, PMF_EINVAL, "pmf_sivm_get_volumes: SIVM contexts under sivm_sgreedy only");
+  if (!c->sv_have_select || !c->sg_have_vol) return fail(c, PMF_EINVAL, "pmf_sivm_get_volumes: no selection yet (update_w has not run)");
+  HIPCHK(c, hipSetDevice(c->device));
+  return sgreedy_get_volumes(c, volumes);
 }
 
 int pmf_greedy_select(pmf_ctx* c, int32_t transposed, int32_t nsel, int32_t* select) {
@@ -1166,11 +1176,21 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
     if (c->algo != PMF_ALGO_SIVM) return fail(c, PMF_EINVAL, "sivm_rule / gmap_method: SIVM contexts only");
     if (name[0] == 's') {
       if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "sivm_rule: 0 (SIVM), 1 (LAESA) or 2 (GMAP)");
+      if (value != 0 && c->sv_sgreedy) return fail(c, PMF_EINVAL, "sivm_rule: LAESA and GMAP not together with sivm_sgreedy");
       c->sv_rule = (int)value;
     } else {
       if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "gmap_method: 0 (pca), 1 (aa) or 2 (nmf)");
       c->sv_gmap_method = (int)value;
     }
+    choose_stat_site(c, false);
+    return PMF_OK;
+  }
+  if (std::strcmp(name, "sivm_sgreedy") == 0) {
+    if (c->algo != PMF_ALGO_SIVM) return fail(c, PMF_EINVAL, "sivm_sgreedy: SIVM contexts only");
+    if (value != 0 && value != 1) return fail(c, PMF_EINVAL, "sivm_sgreedy: 0 or 1");
+    if (value == 1 && c->sv_rule != 0) return fail(c, PMF_EINVAL, "sivm_sgreedy: not together with sivm_rule 1 (LAESA) or 2 (GMAP)");
+    if ((int)value != c->sv_sgreedy) c->sg_have_vol = false;
+    c->sv_sgreedy = (int)value;
     choose_stat_site(c, false);
     return PMF_OK;
   }

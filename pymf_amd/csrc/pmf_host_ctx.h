@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_SIVM_ROWS, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY, SITE_CUR_LEV, SITE_CUR_SQNORMS, SITE_LAESA, SITE_GMAP };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_SIVM_ROWS, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY, SITE_CUR_LEV, SITE_CUR_SQNORMS, SITE_LAESA, SITE_GMAP, SITE_SGREEDY };
 
 struct KernelStat {
   std::string name = "none";
@@ -172,6 +172,12 @@ struct pmf_ctx {
   int sv_rule = 0;              // pmf_set_option("sivm_rule"): 0 SIVM, 1 LAESA, 2 GMAP (pmf_colsel.h) -- what pmf_update_w selects by
   int sv_gmap_method = 0;       // pmf_set_option("gmap_method"): 0 pca, 1 aa, 2 nmf
   bool sv_have_select = false;  // dSvSel holds the selection of a W step
+  // SIVM_SGREEDY (pmf_sgreedy.h): the squared distances to the selected columns ([64][np] float32), inv(CM_S) [64][64], the
+  // rounds' volumes and scale_t; allocated by the first selection under the option
+  float* dSgTab = nullptr;
+  double *dSgM = nullptr, *dSgVol = nullptr;
+  int sv_sgreedy = 0;           // pmf_set_option("sivm_sgreedy"): pmf_update_w selects by the exact simplex volume (sv_rule stays 0)
+  bool sg_have_vol = false;     // dSgVol holds the volumes of a W step
   int opt_profile_sivm_rows = 0;   // pmf_set_option("profile_sivm_rows"): pmf_profile_enable times the rounds of the long-sample pass (SITE_SIVM_ROWS)
   // AA (pmf_aa.h): W_hat, the points X and residuals R ([mp][KP]); the two partials arrays of the pricing pass ([2][wgs][KP]); per
   // base the corral's Gram matrix, data columns and weights by slot, the finished flag; unfinished bases per round; the

@@ -24,6 +24,18 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.name = buf;
     st.flops = st.exec_flops = 4.0 * m * n * k;                  // W^T V and V H^T
     st.bytes = 4.0 * (m * n + k * n + 2.0 * m * k);              // V once, H written, W read, the sums written
+  } else if (c->algo == PMF_ALGO_SIVM && c->sv_sgreedy) {
+    st.site = SITE_SGREEDY;
+    st.name = "k_sgreedy_pass";
+    // round t = 1 .. k - 1: the differences as k_laesa_pass<l2>; the form's (t + 1)^2 products for each column
+    // bytes: V once, the new table row written, rows 0 .. t - 2 read back -- the mean over the rounds
+    double fl = 0.0, by = 0.0;
+    for (int t = 1; t < c->k; ++t) {
+      fl += 3.0 * m * n + 2.0 * (double)(t + 1) * (double)(t + 1) * n;
+      by += 4.0 * m * (double)c->np + 4.0 * (double)c->np + 4.0 * (double)(t - 1) * (double)c->np;
+    }
+    st.flops = st.exec_flops = c->k > 1 ? fl / (double)(c->k - 1) : 0.0;
+    st.bytes = c->k > 1 ? by / (double)(c->k - 1) : 0.0;
   } else if (c->algo == PMF_ALGO_SIVM && c->sv_rule == 1) {
     st.site = SITE_LAESA;
     snprintf(buf, sizeof(buf), "k_laesa_pass<%s>", c->sv_metric == 0 ? "l2" : c->sv_metric == 1 ? "l1" : "cosine");

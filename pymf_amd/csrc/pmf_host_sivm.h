@@ -98,13 +98,17 @@ int gather_selected_w(pmf_ctx* c) {
 // the round drivers of the other two rules of a SIVM context (pmf_host_colsel.h)
 int laesa_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, const SivmBufs& b);
 int gmap_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int method, const SivmBufs& b);
+// ... and of SIVM_SGREEDY (pmf_host_sgreedy.h)
+int sgreedy_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, const SivmBufs& b);
 
-// SIVM.update_w (sivm.py:145-201), LAESA.update_w (laesa.py:63-82) or GMAP.update_w (gmap.py:119-165) by the context's rule:
+// SIVM.update_w (sivm.py:145-201), LAESA.update_w (laesa.py:63-82) or GMAP.update_w (gmap.py:119-165) by the context's rule, or
+// SIVM_SGREEDY.update_w (sivm_sgreedy.py:96-133) under "sivm_sgreedy":
 // the rounds on the resident V and buffers, then the gather
 int sivm_update_w(pmf_ctx* c) {
   PMFCHK(sivm_alloc(c));
   const SivmBufs b{c->dSvState, c->dSvPart, c->dSvPartIdx, c->dSvScal, c->dSvSel};
-  if (c->sv_rule == 1) PMFCHK(laesa_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_metric, c->sv_init == 1, b));
+  if (c->sv_sgreedy) PMFCHK(sgreedy_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_metric, c->sv_init == 1, b));
+  else if (c->sv_rule == 1) PMFCHK(laesa_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_metric, c->sv_init == 1, b));
   else if (c->sv_rule == 2) PMFCHK(gmap_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_gmap_method, b));
   else PMFCHK(sivm_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_metric, c->sv_init == 1, b));
   return gather_selected_w(c);
