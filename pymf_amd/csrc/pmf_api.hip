@@ -21,6 +21,7 @@
 #include <string>
 #include <atomic>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pymf_hip.h"

@@ -19,8 +19,7 @@
 // w = (G[:, i] - sum_s w_s[i] w_s) / sqrt(d_i),  d -= w o w,  C' -= (C'[:, i] / sqrt(d_i)) w^T.  One workgroup.
 // Two runs give the same bits.
 #pragma once
-#include "pmf_dev.h"
-#include "pmf_sivm.h"
+#include "pmf_colsweep.h"   // sivm_better, sivm_wg_best, sivm_reduce_partials
 
 constexpr int PMF_GREEDY_MAX_BASES = 64;
 constexpr int PMF_GREEDY_OPW = 128;         // columns of the staged operand: c + i <= 2 * 64 - 1
@@ -166,7 +165,6 @@ __global__ __launch_bounds__(256) void k_greedy_step(const GreedyStepArgs a) {
   double best;
   int idx;
   sivm_reduce_partials(a.pscore, a.pidx, a.nparts, a.n, sb, ib, &best, &idx);
-  if ((unsigned)idx >= (unsigned)a.n) idx = 0;
   if (tid == 0) { a.select[i] = idx; a.taken[idx] = 1; }
   for (int r = tid; r < m; r += 256) rv[r] = (double)a.A[(int64_t)r * a.ld + idx];
   __syncthreads();

@@ -24,27 +24,17 @@ size_t sgreedy_pass_smem(int R, int t) {
 // k_sgreedy_pass, then the closing reduce, which also leaves the last round's volume.  Nothing is read by the host in between.
 int sgreedy_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, const SivmBufs& b) {
   PMFCHK(sgreedy_alloc(c));
-  int ppw = 0, wgs = 0;
-  panel_partition((int)(ld / 64), PMF_CL_MAX_WGS, &ppw, &wgs);
-  const dim3 grid((unsigned)wgs), block(256);
-  size_t p = 0;
-
-  ColselArgs l = colsel_args(A, ld, R, C, b, ppw);
+  ColselArgs l{};
+  PanelChain ch = colsel_begin(l, A, ld, R, C, b);
   l.fixed_idx = origin ? -1 : 0;
   l.sel_pos = -1; l.plain = 1;
-  for (int q = 0; q < (origin ? 1 : 3); ++q, ++p) {
-    colsel_flip(l, b, p, wgs);
-    l.use_fixed = p == 0;
-    const size_t smem = (size_t)R * sizeof(float);
-    switch (metric) {
-      case PMF_SIVM_L2: hipLaunchKernelGGL(k_laesa_pass<PMF_SIVM_L2>, grid, block, smem, c->stream, l); break;
-      case PMF_SIVM_L1: hipLaunchKernelGGL(k_laesa_pass<PMF_SIVM_L1>, grid, block, smem, c->stream, l); break;
-      default: hipLaunchKernelGGL(k_laesa_pass<PMF_SIVM_COSINE>, grid, block, smem, c->stream, l); break;
-    }
+  for (int q = 0; q < (origin ? 1 : 3); ++q) {
+    l.use_fixed = chain_next(ch, l) == 0;
+    laesa_launch_pass(c, l, ch.wgs, metric);
     HIPCHK(c, hipGetLastError());
   }
   c->sg_have_vol = true;
-  if (nsel == 1) return colsel_close(c, b, p, wgs, C, nsel, 1, origin ? 1 : 0);
+  if (nsel == 1) return chain_close(c, ch, C, 0, true, origin, b.scal);
 
   const size_t smem_max = sgreedy_pass_smem(PMF_SIVM_MAX_M, PMF_SGREEDY_MAX_T - 1);
   static bool attr_done_dev[PMF_MAX_DEVICES] = {};      // the attribute is per device
@@ -54,29 +44,23 @@ int sgreedy_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, i
     attr_done = true;
   }
   SgreedyArgs a{};
-  a.V = A; a.d2 = c->dSgTab; a.M = c->dSgM; a.sc = c->dSgVol + PMF_SGREEDY_MAX_T + 2; a.vol = c->dSgVol;
+  static_cast<ColsweepArgs&>(a) = l;               // the same matrix and partition
+  a.d2 = c->dSgTab; a.M = c->dSgM; a.sc = c->dSgVol + PMF_SGREEDY_MAX_T + 2; a.vol = c->dSgVol;
   a.select = b.select;
-  a.np = ld; a.m = R; a.n = C;
-  a.npanels = (int)(ld / 64); a.panels_per_wg = ppw;
-  a.nprev = wgs; a.origin = origin ? 1 : 0;
-  for (int t = 1; t < nsel; ++t, ++p) {
-    const int out = (int)(p & 1), in = out ^ 1;
-    a.pscore_in = b.part + in * PMF_CL_MAX_WGS; a.pidx_in = b.pidx + in * PMF_CL_MAX_WGS;
-    a.pscore_out = b.part + out * PMF_CL_MAX_WGS; a.pidx_out = b.pidx + out * PMF_CL_MAX_WGS;
+  a.origin = origin ? 1 : 0;
+  for (int t = 1; t < nsel; ++t) {
+    chain_next(ch, a);                             // (the step reads the partials its pass reads)
     a.t = t;
-    hipLaunchKernelGGL(k_sgreedy_step, dim3(1), block, 0, c->stream, a);
+    hipLaunchKernelGGL(k_sgreedy_step, dim3(1), dim3(256), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     stat_begin(c, SITE_SGREEDY);
-    hipLaunchKernelGGL(k_sgreedy_pass, grid, block, sgreedy_pass_smem(R, t), c->stream, a);
+    hipLaunchKernelGGL(k_sgreedy_pass, dim3((unsigned)ch.wgs), dim3(256), sgreedy_pass_smem(R, t), c->stream, a);
     stat_end(c, SITE_SGREEDY);
     HIPCHK(c, hipGetLastError());
   }
   // the last argmax into select[nsel - 1]; its score -- the last round's volume -- into vol[nsel - 2] (k_sivm_close's maxd slot;
   // the logarithm it stores next to it lands in the unused slot behind)
-  const int last = (int)((p - 1) & 1);
-  hipLaunchKernelGGL(k_sivm_close, dim3(1), dim3(256), 0, c->stream, (const double*)(b.part + last * PMF_CL_MAX_WGS),
-                     (const int*)(b.pidx + last * PMF_CL_MAX_WGS), wgs, C, nsel - 1, 1, 0, b.select, c->dSgVol + (nsel - 2));
-  HIPCHK(c, hipGetLastError());
+  PMFCHK(chain_close(c, ch, C, nsel - 1, true, false, c->dSgVol + (nsel - 2)));
   // the reference's order of select, so that W = V[:, select] and the rows of H are in it too
   hipLaunchKernelGGL(k_sgreedy_order, dim3(1), dim3(64), 0, c->stream, b.select, nsel);
   HIPCHK(c, hipGetLastError());

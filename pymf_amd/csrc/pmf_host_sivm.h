@@ -21,16 +21,22 @@ int sivm_alloc(pmf_ctx* c) {
   return PMF_OK;
 }
 
+// f(std::integral_constant<int, M>) for the runtime metric (or GMAP method) M = 0, 1, 2: the kernels take it as a template argument
+template <class F>
+void with_metric(int metric, F f) {
+  switch (metric) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    default: f(std::integral_constant<int, 2>{}); break;
+  }
+}
+
 // one k_sivm_pass over the matrix that `a` describes (a.m rows staged in LDS)
 int sivm_launch_pass(pmf_ctx* c, const SivmArgs& a, int wgs, int metric) {
-  const dim3 grid((unsigned)wgs), block(256);
-  const size_t smem = (size_t)a.m * sizeof(float);
   stat_begin(c, SITE_SIVM);
-  switch (metric) {
-    case PMF_SIVM_L2: hipLaunchKernelGGL(k_sivm_pass<PMF_SIVM_L2>, grid, block, smem, c->stream, a); break;
-    case PMF_SIVM_L1: hipLaunchKernelGGL(k_sivm_pass<PMF_SIVM_L1>, grid, block, smem, c->stream, a); break;
-    default: hipLaunchKernelGGL(k_sivm_pass<PMF_SIVM_COSINE>, grid, block, smem, c->stream, a); break;
-  }
+  with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL(k_sivm_pass<decltype(M)::value>, dim3((unsigned)wgs), dim3(256), (size_t)a.m * sizeof(float), c->stream, a);
+  });
   stat_end(c, SITE_SIVM);
   HIPCHK(c, hipGetLastError());
   return PMF_OK;
@@ -53,35 +59,52 @@ std::vector<SivmRound> sivm_rounds(int nsel, bool origin) {
 // each), (maxd, a) and the selection -- the resident buffers of the context (update_w) or temporaries of a pmf_sivm_select call
 struct SivmBufs { double* state; double* part; int* pidx; double* scal; int* select; };
 
-// k_sivm_pass on A [R rows][ld], candidates its C columns: nsel + 2 ('fastmap') or nsel ('origin') launches back to back and the
-// closing reduce; a round's argmax is taken in the next launch's prologue, nothing is read by the host in between
-int sivm_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, const SivmBufs& b) {
-  int ppw = 0, wgs = 0;
-  panel_partition((int)(ld / 64), PMF_CL_MAX_WGS, &ppw, &wgs);
-  HIPCHK(c, hipMemsetAsync(b.state, 0, (size_t)3 * ld * sizeof(double), c->stream));
-  SivmArgs a{};
-  a.V = A;
-  a.dij = b.state; a.dsum = b.state + ld; a.dsq = b.state + 2 * ld;
-  a.select = b.select; a.scal = b.scal;
-  a.np = ld; a.m = R; a.n = C;
-  a.npanels = (int)(ld / 64); a.panels_per_wg = ppw;
-  a.fixed_idx = origin ? -1 : 0;
-  const std::vector<SivmRound> rounds = sivm_rounds(nsel, origin);
-  for (size_t p = 0; p < rounds.size(); ++p) {
-    const SivmRound& r = rounds[p];
-    const int out = (int)(p & 1), in = out ^ 1;
-    a.pscore_in = b.part + in * PMF_CL_MAX_WGS; a.pidx_in = b.pidx + in * PMF_CL_MAX_WGS;
-    a.pscore_out = b.part + out * PMF_CL_MAX_WGS; a.pidx_out = b.pidx + out * PMF_CL_MAX_WGS;
-    a.nprev = p == 0 ? 0 : wgs;
-    a.use_fixed = p == 0 || (origin && r.l == 1);
-    a.sel_pos = r.sel_pos; a.take_maxd = r.l == 1; a.plain = r.plain; a.l = r.l;
-    PMFCHK(sivm_launch_pass(c, a, wgs, metric));
-  }
-  const int last = (int)((rounds.size() - 1) & 1);
-  hipLaunchKernelGGL(k_sivm_close, dim3(1), dim3(256), 0, c->stream, (const double*)(b.part + last * PMF_CL_MAX_WGS),
-                     (const int*)(b.pidx + last * PMF_CL_MAX_WGS), wgs, C, nsel - 1, nsel == 1 ? 1 : 0, (origin && nsel == 1) ? 1 : 0, b.select, b.scal);
+// A chain of column-panel launches on A [R rows][ld], candidates its C columns, as every driver of the family enqueues one
+// (pmf_colsweep.h): a round's argmax is taken in the next launch's prologue, nothing is read by the host in between.
+struct PanelChain { const SivmBufs& b; int wgs; size_t p; };   // the buffers, the workgroups of a launch, launches so far
+
+// the partition, and what of the common argument block stays the same along the chain
+PanelChain chain_begin(ColsweepArgs& a, const float* A, int64_t ld, int R, int C, const SivmBufs& b) {
+  int wgs = 0;
+  a.V = A; a.np = ld; a.m = R; a.n = C;
+  a.npanels = (int)(ld / 64);
+  panel_partition(a.npanels, PMF_CL_MAX_WGS, &a.panels_per_wg, &wgs);
+  return {b, wgs, 0};
+}
+
+// the next launch reads the partials that the one before it wrote; returns its number in the chain
+size_t chain_next(PanelChain& ch, ColsweepArgs& a) {
+  const int out = (int)(ch.p & 1), in = out ^ 1;
+  a.pscore_in = ch.b.part + in * PMF_CL_MAX_WGS; a.pidx_in = ch.b.pidx + in * PMF_CL_MAX_WGS;
+  a.pscore_out = ch.b.part + out * PMF_CL_MAX_WGS; a.pidx_out = ch.b.pidx + out * PMF_CL_MAX_WGS;
+  a.nprev = ch.p == 0 ? 0 : ch.wgs;
+  return ch.p++;
+}
+
+// the reduce behind the last launch: select[sel_pos]; take_maxd: its score and the logarithm of it into scal[0], scal[1]
+int chain_close(pmf_ctx* c, const PanelChain& ch, int C, int sel_pos, bool take_maxd, bool origin_first, double* scal) {
+  const int last = (int)((ch.p - 1) & 1);
+  hipLaunchKernelGGL(k_sivm_close, dim3(1), dim3(256), 0, c->stream, (const double*)(ch.b.part + last * PMF_CL_MAX_WGS),
+                     (const int*)(ch.b.pidx + last * PMF_CL_MAX_WGS), ch.wgs, C, sel_pos, take_maxd ? 1 : 0, origin_first ? 1 : 0, ch.b.select, scal);
   HIPCHK(c, hipGetLastError());
   return PMF_OK;
+}
+
+// k_sivm_pass: nsel + 2 ('fastmap') or nsel ('origin') launches back to back and the closing reduce
+int sivm_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, const SivmBufs& b) {
+  HIPCHK(c, hipMemsetAsync(b.state, 0, (size_t)3 * ld * sizeof(double), c->stream));
+  SivmArgs a{};
+  PanelChain ch = chain_begin(a, A, ld, R, C, b);
+  a.dij = b.state; a.dsum = b.state + ld; a.dsq = b.state + 2 * ld;
+  a.select = b.select; a.scal = b.scal;
+  a.fixed_idx = origin ? -1 : 0;
+  for (const SivmRound& r : sivm_rounds(nsel, origin)) {
+    const size_t p = chain_next(ch, a);
+    a.use_fixed = p == 0 || (origin && r.l == 1);
+    a.sel_pos = r.sel_pos; a.take_maxd = r.l == 1; a.plain = r.plain; a.l = r.l;
+    PMFCHK(sivm_launch_pass(c, a, ch.wgs, metric));
+  }
+  return chain_close(c, ch, C, nsel - 1, nsel == 1, origin && nsel == 1, b.scal);
 }
 
 // W = V[:, select] for the selection in dSvSel (SIVM, GREEDY)
@@ -162,11 +185,7 @@ int sivm_select_rows(pmf_ctx* c, const float* A, int64_t ld, int C, int R, int n
   }
   for (const SivmRound& r : sivm_rounds(nsel, origin)) {
     stat_begin(c, SITE_SIVM_ROWS);
-    switch (metric) {
-      case PMF_SIVM_L2: sivm_launch_rowdist<PMF_SIVM_L2>(c, d); break;
-      case PMF_SIVM_L1: sivm_launch_rowdist<PMF_SIVM_L1>(c, d); break;
-      default: sivm_launch_rowdist<PMF_SIVM_COSINE>(c, d); break;
-    }
+    with_metric(metric, [&](auto M) { sivm_launch_rowdist<decltype(M)::value>(c, d); });
     HIPCHK(c, hipGetLastError());
     s.plain = r.plain; s.l = r.l; s.take_maxd = r.take_maxd; s.keep_cur = r.keep; s.sel_pos = r.sel_pos;
     s.last_pos = r.last ? nsel - 1 : -1;

@@ -9,13 +9,11 @@
 // work is t + 1 squared l2 distances and one quadratic form (k_sgreedy_pass).  S is kept in selection order through the rounds:
 // the determinant does not depend on the order; k_sgreedy_order puts `select` into the reference's order behind the last round.
 //
-// k_sgreedy_pass  one launch per round on k_sivm_pass's partition (a workgroup: a range of 64-column panels, a lane: 4 adjacent
-//   columns, x = the newest selected column in dynamic LDS, behind it M).  The fp32 squared l2 distance to x is colsel_sums'
-//   difference sum (what k_laesa_pass<l2> takes the root of); it becomes row t - 1 of the float32 table d2 [64][np]; rows
-//   0 .. t - 1 are read back and b^T M b is formed in float64 on the vector unit in 8 x 8 blocks of M: a lane holds two blocks
-//   of b (8 entries x 4 columns each, compile-time indexed) and walks the lower block triangle, the off-diagonal blocks
-//   counting twice.  score = sqrt(|scale_t form|), scale_t = |f1(t) det(CM_S)|; argmax chain as every pass of the family
-//   (sivm_better, sivm_wg_best, partials, the next launch's prologue).
+// k_sgreedy_pass  one launch per round on the sweep of pmf_colsweep.h (x = the newest selected column in dynamic LDS, behind it
+//   M).  The fp32 squared l2 distance to x is colsweep_sums' difference sum (what k_laesa_pass<l2> takes the root of); it
+//   becomes row t - 1 of the float32 table d2 [64][np]; rows 0 .. t - 1 are read back and b^T M b is formed in float64 on the
+//   vector unit in 8 x 8 blocks of M: a lane holds two blocks of b (8 entries x 4 columns each, compile-time indexed) and walks
+//   the lower block triangle, the off-diagonal blocks counting twice.  score = sqrt(|scale_t form|), scale_t = |f1(t) det(CM_S)|.
 // k_sgreedy_step  one workgroup between two passes: the argmax of the previous launch is s_t (its score the volume of the round
 //   before: _v); CM_S is gathered from the table -- d^2(s_i, s_j) = d2[i - 1][s_j], i < j, the very fp32 values the candidates
 //   see, so a candidate equal to a selected column scores rounding-level zero -- and inverted in place in LDS by Gauss-Jordan
@@ -23,26 +21,17 @@
 //   underflows on its own.  A singular CM_S (S affinely dependent: num_bases > rows + 1) gives a non-finite M; such scores never
 //   win (sivm_better), the prologue's index stays inside [0, n).
 #pragma once
-#include "pmf_colsel.h"
+#include "pmf_colsweep.h"
 
 constexpr int PMF_SGREEDY_MAX_T = 64;    // order of CM_S at the last round: 63 selected columns and the border
 constexpr int PMF_SGREEDY_BLK = 8;       // block edge of the quadratic form
 
-struct SgreedyArgs {
-  const float* V;          // [mp][np]
+struct SgreedyArgs : ColsweepArgs {
   float* d2;               // [64][np] squared l2 distances: row r to the (r + 1)-th selected column
   double* M;               // [64][64] inv(CM_S), zero outside its (t + 1) x (t + 1)
   double* sc;              // [0] scale_t
   double* vol;             // [64] the volumes of the rounds (_v)
-  const double* pscore_in; // partials of the previous launch ...
-  const int* pidx_in;
-  double* pscore_out;      // ... and of this pass, [wgs]
-  int* pidx_out;
   int* select;             // [k] in selection order
-  int64_t np;
-  int m, n;
-  int npanels, panels_per_wg;
-  int nprev;               // partials of the previous launch
   int t;                   // columns selected so far (this round finds the (t + 1)-th)
   int origin;              // init = 'origin': select[0] = -1, the first vertex is the LAST data column (sivm_sgreedy.py:99,109)
 };
@@ -174,20 +163,16 @@ __global__ __launch_bounds__(256) void k_sgreedy_pass(const SgreedyArgs a) {
   const int idx = sgreedy_newest(a, sb, ib, &best);
   const double scale = a.sc[0];
 
-  const int c_begin = blockIdx.x * a.panels_per_wg * 64;
-  const int c_end = min((blockIdx.x + 1) * a.panels_per_wg, a.npanels) * 64;
-  const int nquads = (c_end - c_begin) / 4;
   for (int e = tid; e < TP * TP; e += 256) Ms[e] = a.M[(e / TP) * PMF_SGREEDY_MAX_T + e % TP];
-  colsel_stage_x(a.V, a.np, a.m, idx, xs);
+  colsweep_stage_x(a, idx, xs);
 
   float* const newrow = a.d2 + (int64_t)(t - 1) * a.np;
   double bs = -INFINITY;
   int bidx = 0x7fffffff;
-  for (int q = tid; q < nquads; q += 256) {
-    const int c = c_begin + 4 * q;
+  colsweep_quads(a, [&](const int c) __attribute__((always_inline)) {
     f32x4 st, nt;
     float xx;
-    colsel_sums<PMF_SIVM_L2>(a.V + c, a.np, a.m, xs, st, nt, xx);
+    colsweep_sums<PMF_SIVM_L2>(a, c, xs, st, nt, xx);
     *reinterpret_cast<f32x4*>(newrow + c) = st;
 
     // entry e of b for the lane's 4 columns: 1, then the table's rows 0 .. t - 1 (row t - 1 is st), zero behind them
@@ -244,7 +229,6 @@ __global__ __launch_bounds__(256) void k_sgreedy_pass(const SgreedyArgs a) {
 #pragma unroll
     for (int x = 0; x < 4; ++x)
       if (c + x < a.n) sivm_better(bs, bidx, sqrt(fabs(scale * form[x])), c + x);
-  }
-  sivm_wg_best(bs, bidx, sb, ib);
-  if (tid == 0) { a.pscore_out[blockIdx.x] = bs; a.pidx_out[blockIdx.x] = bidx; }
+  });
+  colsweep_finish(a, bs, bidx, sb, ib);
 }

@@ -3,83 +3,39 @@
 //
 // update_w (sivm.py:145-201) is num_bases + 2 ('fastmap') or num_bases ('origin') dependent passes over V [mp][np]: the
 // distance of every column to ONE selected column x = V[:, idx], a pointwise recurrence on three float64 arrays, an argmax.
-// k_sivm_pass<METRIC> is one such pass.  A workgroup owns a contiguous range of 64-column panels (a lane: 4 adjacent columns,
-// one 16-byte read per row, walking down the rows); x is gathered into LDS once per launch (idx = -1: x = 0, the 'origin'
-// initialisation, no gather).  The distance is formed from the difference, as dist.py:57-63 does, in fp32 with four
-// independent partial sums per column:  l2 sqrt(sum (v - x)^2),  l1 sum |v - x|,  cosine 1 - v.x / (|v| |x| + 1e-9).
-// Recurrence (sivm.py:181-190, float64), d = log(dist + 1e-8):
+// k_sivm_pass<METRIC> is one such pass on the sweep of pmf_colsweep.h (work decomposition, fp32 sums, argmax chain).  The
+// distance is formed from the difference, as dist.py:57-63 does:  l2 sqrt(sum (v - x)^2),  l1 sum |v - x|,
+// cosine 1 - v.x / (|v| |x| + 1e-9).  Recurrence (sivm.py:181-190, float64; sivm_recur), d = log(dist + 1e-8):
 //   d_i_times_d_j += d d_sum;  d_sum += d;  d_square += d^2;  score = d_i_times_d_j + a d_sum - (l / 2) d_square
-// with a = log(maxd).  The three fastmap passes (sivm.py:153-155) run the same kernel "plain": score = dist, state untouched.
-// Argmax without a host round trip and without float atomics: every workgroup writes (best score, lowest column attaining
-// it) into a partials array; the NEXT launch reduces the <= PMF_CL_MAX_WGS partials in its prologue -- every workgroup the
-// same way, the lowest index winning ties -- and works on that idx; workgroup 0 appends it to select[] and, behind the last
-// plain pass, writes maxd and a.  k_sivm_close does the last reduce, k_sivm_gather writes W = V[:, select] (a -1 entry is a
-// Python index there: the LAST data column).  Pad columns (c >= n) never win.  Two runs give the same bits.
+// with a = log(maxd).  The three fastmap passes (sivm.py:153-155) run the same kernel "plain": score = dist, state untouched;
+// behind the last of them workgroup 0 writes maxd and a.  k_sivm_close does the last reduce, k_sivm_gather writes
+// W = V[:, select] (a -1 entry is a Python index there: the LAST data column).
 // The same selection among the ROWS of a row-major matrix, whose samples are too long for LDS, is the long-sample pass
 // further down (k_sivm_rowdist, k_sivm_rowstep): SIVM_CUR's row selection.
 #pragma once
-#include "pmf_dev.h"
+#include "pmf_colsweep.h"
 
-enum { PMF_SIVM_L2 = 0, PMF_SIVM_L1 = 1, PMF_SIVM_COSINE = 2 };
 constexpr int PMF_SIVM_MAX_M = 16384;   // x is staged whole in LDS (m floats of dynamic shared memory: 64 KiB at the limit)
 
-struct SivmArgs {
-  const float* V;          // [mp][np]
+struct SivmArgs : ColsweepPickArgs {
   double* dij;             // [np] d_i_times_d_j
   double* dsum;            // [np] d_sum
   double* dsq;             // [np] d_square
-  const double* pscore_in; // partials of the previous launch ...
-  const int* pidx_in;
-  double* pscore_out;      // ... and of this one, [wgs]
-  int* pidx_out;
-  int* select;             // [k]
-  double* scal;            // [0] maxd, [1] a = log(maxd)
-  int64_t np;
-  int m, n;
-  int npanels, panels_per_wg;
-  int nprev;               // partials of the previous launch to reduce in the prologue (0: none)
-  int use_fixed;           // idx = fixed_idx (the first fastmap pass: column 0; 'origin': -1) instead of the prologue's argmax
-  int fixed_idx;
-  int sel_pos;             // >= 0: workgroup 0 writes select[sel_pos] = idx
-  int take_maxd;           // the best score of the previous (plain) launch is maxd: a = log of it, workgroup 0 stores both
   int plain;               // score = dist, state untouched
   int l;                   // step of the recurrence (sivm.py:181)
 };
 
-// (score, index): a greater score wins, then the lower index
-__device__ __forceinline__ void sivm_better(double& s, int& i, double os, int oi) {
-  if (os > s || (os == s && oi < i)) { s = os; i = oi; }
-}
-
-// the workgroup's best of (s, i) over its 256 threads, in thread 0 (and in sb[0], ib[0])
-__device__ __forceinline__ void sivm_wg_best(double& s, int& i, double* sb, int* ib) {
-#pragma unroll
-  for (int x = 1; x < 64; x <<= 1) {
-    const double os = __shfl_xor(s, x);
-    const int oi = __shfl_xor(i, x);
-    sivm_better(s, i, os, oi);
-  }
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { sb[wave] = s; ib[wave] = i; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) sivm_better(s, i, sb[w], ib[w]);
-    sb[0] = s; ib[0] = i;
-  }
-  __syncthreads();
-}
-
-// the argmax over the previous launch's partials (every workgroup alike); n: an index outside [0, n) -- no finite score at
-// all -- becomes 0, so that nothing is ever gathered from outside V
-__device__ __forceinline__ void sivm_reduce_partials(const double* ps, const int* pi, int count, int n, double* sb, int* ib,
-                                                     double* best, int* idx) {
-  double s = -INFINITY;
-  int i = 0x7fffffff;
-  for (int q = threadIdx.x; q < count; q += 256) sivm_better(s, i, ps[q], pi[q]);
-  sivm_wg_best(s, i, sb, ib);
-  *best = sb[0];
-  *idx = ((unsigned)ib[0] < (unsigned)n) ? ib[0] : 0;
+// candidate i's step of the recurrence: its three states updated, its score returned
+__device__ __forceinline__ double sivm_recur(double dist, double a_log, double hl, double* dij, double* dsum, double* dsq, int i) {
+  const double d = log(dist + 1e-8);
+  const double ds_old = dsum[i];
+  const double ij = dij[i] + d * ds_old;
+  const double ds = ds_old + d;
+  const double dq = dsq[i] + d * d;
+  dij[i] = ij;
+  dsum[i] = ds;
+  dsq[i] = dq;
+  return ij + a_log * ds - hl * dq;
 }
 
 template <int METRIC>
@@ -87,105 +43,30 @@ __global__ __launch_bounds__(256) void k_sivm_pass(const SivmArgs a) {
   extern __shared__ float xs[];                 // [m]
   __shared__ double sb[4];
   __shared__ int ib[4];
-  const int tid = threadIdx.x;
-  const int64_t np = a.np;
-
-  // ---- prologue: which column this pass measures against ----------------------------------------------------------
-  int idx = a.fixed_idx;
-  double a_log = 0.0;
-  if (a.nprev > 0) {
-    double best;
-    int bi;
-    sivm_reduce_partials(a.pscore_in, a.pidx_in, a.nprev, a.n, sb, ib, &best, &bi);
-    if (!a.use_fixed) idx = bi;
-    if (a.take_maxd) {
-      a_log = log(best);
-      if (blockIdx.x == 0 && tid == 0) { a.scal[0] = best; a.scal[1] = a_log; }
-    }
-  }
+  double a_log;
+  const int idx = colsweep_pick(a, sb, ib, &a_log);
   if (!a.take_maxd && !a.plain) a_log = a.scal[1];
-  if (blockIdx.x == 0 && tid == 0 && a.sel_pos >= 0) a.select[a.sel_pos] = idx;
-
-  const int c_begin = blockIdx.x * a.panels_per_wg * 64;
-  const int c_end = min((blockIdx.x + 1) * a.panels_per_wg, a.npanels) * 64;
-  const int nquads = (c_end - c_begin) / 4;
-  const float* xcol = a.V + (idx >= 0 ? idx : 0);
+  const double hl = 0.5 * (double)a.l;
+  colsweep_stage_x(a, idx, xs);
 
   double bs = -INFINITY;
   int bidx = 0x7fffffff;
-  for (int r = tid; r < a.m; r += 256) xs[r] = idx >= 0 ? xcol[(int64_t)r * np] : 0.f;
-  __syncthreads();
-
-  for (int q = tid; q < nquads; q += 256) {
-    const int c = c_begin + 4 * q;
-    const float* vp = a.V + c;
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;        // l2 / l1: the distance sums; cosine: v . x
-    f32x4 n0 = s0, n1 = s0, n2 = s0, n3 = s0;                          // cosine: |v|^2
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f, x3 = 0.f;                      // cosine: |x|^2
-    auto step = [&](const f32x4 v, const float x, f32x4& s, f32x4& nn, float& xx) {
-      if (METRIC == PMF_SIVM_L2) {
-        const f32x4 d = v - x;
-        s += d * d;
-      } else if (METRIC == PMF_SIVM_L1) {
-        const f32x4 d = v - x;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[e] += fabsf(d[e]);
-      } else {
-        s += v * x;
-        nn += v * v;
-        xx = fmaf(x, x, xx);
-      }
-    };
-    int r = 0;
-    for (; r + 4 <= a.m; r += 4) {
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 0) * np);
-      const f32x4 v1 = *reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 1) * np);
-      const f32x4 v2 = *reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 2) * np);
-      const f32x4 v3 = *reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 3) * np);
-      step(v0, xs[r + 0], s0, n0, x0);
-      step(v1, xs[r + 1], s1, n1, x1);
-      step(v2, xs[r + 2], s2, n2, x2);
-      step(v3, xs[r + 3], s3, n3, x3);
-    }
-    if (r < a.m) step(*reinterpret_cast<const f32x4*>(vp + (int64_t)r * np), xs[r], s0, n0, x0);
-    if (r + 1 < a.m) step(*reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 1) * np), xs[r + 1], s1, n1, x1);
-    if (r + 2 < a.m) step(*reinterpret_cast<const f32x4*>(vp + (int64_t)(r + 2) * np), xs[r + 2], s2, n2, x2);
-    const f32x4 st = (s0 + s1) + (s2 + s3);
-    f32x4 dist;
-    if (METRIC == PMF_SIVM_L2) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dist[e] = sqrtf(st[e]);
-    } else if (METRIC == PMF_SIVM_L1) {
-      dist = st;
-    } else {
-      const f32x4 nt = (n0 + n1) + (n2 + n3);
-      const float xn = sqrtf((x0 + x1) + (x2 + x3));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dist[e] = 1.f - st[e] / (sqrtf(nt[e]) * xn + 1e-9f);
-    }
+  colsweep_quads(a, [&](const int c) __attribute__((always_inline)) {
+    f32x4 st, nt;
+    float xx;
+    colsweep_sums<METRIC>(a, c, xs, st, nt, xx);
+    const f32x4 dist = colsweep_dist<METRIC>(st, nt, xx);
     if (a.plain) {
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         if (c + e < a.n) sivm_better(bs, bidx, (double)dist[e], c + e);
     } else {
-      const double hl = 0.5 * (double)a.l;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (c + e >= a.n) continue;
-        const double d = log((double)dist[e] + 1e-8);
-        const double ds_old = a.dsum[c + e];
-        const double dij = a.dij[c + e] + d * ds_old;
-        const double ds = ds_old + d;
-        const double dq = a.dsq[c + e] + d * d;
-        a.dij[c + e] = dij;
-        a.dsum[c + e] = ds;
-        a.dsq[c + e] = dq;
-        sivm_better(bs, bidx, dij + a_log * ds - hl * dq, c + e);
-      }
+      for (int e = 0; e < 4; ++e)
+        if (c + e < a.n) sivm_better(bs, bidx, sivm_recur((double)dist[e], a_log, hl, a.dij, a.dsum, a.dsq, c + e), c + e);
     }
-  }
-  sivm_wg_best(bs, bidx, sb, ib);
-  if (tid == 0) { a.pscore_out[blockIdx.x] = bs; a.pidx_out[blockIdx.x] = bidx; }
+  });
+  colsweep_finish(a, bs, bidx, sb, ib);
 }
 
 // the reduce behind the last pass: select[sel_pos] (and maxd, a when no recurrence pass followed the plain ones: num_bases = 1)
@@ -418,19 +299,8 @@ __global__ __launch_bounds__(256) void k_sivm_rowstep(const SivmRowStepArgs a) {
       if (a.metric == PMF_SIVM_L2) dist = sqrt(s0);
       else if (a.metric == PMF_SIVM_L1) dist = s0;
       else dist = 1.0 - s0 / (sqrt(s1) * xn + 1e-9);
-      if (a.plain) {
-        sivm_better(bs, bi, dist, r);
-      } else {
-        const double d = log(dist + 1e-8);
-        const double ds_old = a.dsum[r];
-        const double dij = a.dij[r] + d * ds_old;
-        const double ds = ds_old + d;
-        const double dq = a.dsq[r] + d * d;
-        a.dij[r] = dij;
-        a.dsum[r] = ds;
-        a.dsq[r] = dq;
-        sivm_better(bs, bi, dij + a_log * ds - hl * dq, r);
-      }
+      if (a.plain) sivm_better(bs, bi, dist, r);
+      else sivm_better(bs, bi, sivm_recur(dist, a_log, hl, a.dij, a.dsum, a.dsq, r), r);
     }
   }
   sivm_wg_best(bs, bi, sb, ib);

@@ -18,6 +18,7 @@ CASES = {
     "29x300_k6_l1": (29, 300, 6, 22, 0.0, 4.0, "l1", "fastmap", None),
     "29x300_k6_cosine": (29, 300, 6, 52, 0.0, 4.0, "cosine", "fastmap", None),
     "29x300_k6_origin": (29, 300, 6, 12, 0.0, 4.0, "l2", "origin", None),
+    "31x300_k6": (31, 300, 6, 12, 0.0, 4.0, "l2", "fastmap", None),             # 3-row tail (seed 12: the checks hold at it)
     "64x4113_k8": (64, 4113, 8, 13, 0.0, 4.0, "l2", "fastmap", "ends"),
     "130x1000_k12": (130, 1000, 12, 14, 0.0, 4.0, "l2", "fastmap", None),
     "29x300_k6_offset1000": (29, 300, 6, 15, 1000.0, 400.0, "l2", "fastmap", None),
