@@ -273,6 +273,36 @@ int pmf_cluster_set_assigned(pmf_ctx* ctx, const int32_t* assigned);
 int pmf_sivm_get_select(pmf_ctx* ctx, int32_t* select);
 int pmf_sivm_get_volumes(pmf_ctx* ctx, double* volumes);
 
+/* SIVM_GSAT (pymf/sivm_gsat.py:82-125, the online swap-based volume maximisation) runs on the same context under
+ * pmf_set_option "sivm_gsat" (0 default, 1); the option is refused (PMF_EINVAL) on other contexts, out of range and together
+ * with "sivm_rule" 1 or 2 or "sivm_sgreedy".  Under it pmf_update_w refuses: the vertices move through the entries below, which
+ * keep W as the context's W (pmf_get_w_*, pmf_update_h, pmf_frobenius see every swap).  "sivm_metric" 0 'l2' or 1 'l1' is the
+ * measure of the distances between a probe and the vertices; the distances among the vertices are l2 whatever it says, as the
+ * reference mixes them; 2 'cosine' is refused.  Distances and volumes are float64 from the float32 values; pmf_gsat.h.
+ * pmf_gsat_start: the walk's state from the context's W (its num_bases columns are the vertices; pmf_set_w_* first) and
+ *   `select` (num_bases indices: the data column each vertex is, any value outside [0, num_samples) for a vertex that is none):
+ *   the l2 distance table and V = cmdet of it (sivm_gsat.py:84-88); the log of volumes starts empty.  A state that belongs to
+ *   the current W is kept (started = 0 on return) unless force != 0; pmf_set_w_* ends it.  Dense resident data, one rank.
+ * pmf_gsat_walk: n probes, the data columns idx[0 .. n) in this order, each as sivm_gsat.py:119-125 with online_update_w
+ *   behind it: slots_out[i] is the vertex that probe i replaced, -1 for a reject, -2 for a probe that was in `select` when its
+ *   turn came.  Probes are evaluated 256 to a launch (k_gsat_probe) against the current vertices; the first accepted one is
+ *   applied (k_gsat_commit) and the probes behind it are evaluated again, so the verdicts are those of the one-by-one
+ *   sequence.  One 4-byte read per launch pair.  An index outside [0, num_samples) is PMF_EINVAL before anything runs.
+ * pmf_gsat_probe_vec: online_update_w (sivm_gsat.py:82-117) on a vector of data_dimension floats that need not be a data
+ *   column: slot_out is the vertex it replaced or -1; `select` is left as it is, as in the reference.
+ * pmf_gsat_get_volumes: count = the entries of the reference's _v since pmf_gsat_start (0 before the first swap, then the
+ *   volume before the first swap and every accepted volume), the first min(cap, count) of them into volumes (may be NULL
+ *   with cap = 0), and V, the current volume.
+ * pmf_gsat_get_d: the reference's D as it leaves it, (num_bases + 1)^2 float64 row-major: the distance table, in row and
+ *   column num_bases the distances of the last probe that was evaluated (zeros before the first), the corner 0.
+ * pmf_sivm_get_select answers with the walk's `select`.  Decisions are the reference's while num_bases <= data_dimension + 1
+ * on data in general position; beyond that every volume is rounding noise in the reference too: slots and indices stay valid. */
+int pmf_gsat_start(pmf_ctx* ctx, const int32_t* select, int32_t force, int32_t* started);
+int pmf_gsat_walk(pmf_ctx* ctx, const int64_t* idx, int64_t n, int32_t* slots_out);
+int pmf_gsat_probe_vec(pmf_ctx* ctx, const float* vec, int32_t* slot_out);
+int pmf_gsat_get_volumes(pmf_ctx* ctx, double* volumes, int64_t cap, int64_t* count, double* V);
+int pmf_gsat_get_d(pmf_ctx* ctx, double* D);
+
 /* pmf_sivm_select: SIVM's selection alone (pymf/sivm_cur.py:65-73: what SIVM_CUR.sample asks of SIVM) on a SIVM or a CUR / CMD
  * context -- nsel indices in selection order among the columns of V (transposed = 0) or among its rows (transposed = 1: SIVM on
  * the transposed view), under metric 0 'l2', 1 'l1' or 2 'cosine' and init 0 'fastmap' or 1 'origin' (the first entry is then -1).

@@ -69,6 +69,11 @@ SYMBOLS = [
     ("pmf_cluster_set_assigned", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_sivm_get_select", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_sivm_get_volumes", _c.c_int, [_ctx, _c.c_void_p]),
+    ("pmf_gsat_start", _c.c_int, [_ctx, _c.c_void_p, _c.c_int32, _c.POINTER(_c.c_int32)]),
+    ("pmf_gsat_walk", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    ("pmf_gsat_probe_vec", _c.c_int, [_ctx, _c.c_void_p, _c.POINTER(_c.c_int32)]),
+    ("pmf_gsat_get_volumes", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_double)]),
+    ("pmf_gsat_get_d", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_greedy_select", _c.c_int, [_ctx, _c.c_int32, _c.c_int32, _c.c_void_p]),
     ("pmf_sivm_select", _c.c_int, [_ctx, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p]),
     ("pmf_aa_get_beta", _c.c_int, [_ctx, _c.c_void_p]),
@@ -397,6 +402,45 @@ class Context(object):
         out = np.empty(max(self.k - 1, 1), dtype=np.float64)
         self._chk(self._lib.pmf_sivm_get_volumes(self._h, out.ctypes.data))
         return out[:self.k - 1]
+
+    def gsat_start(self, select, force=False):
+        """SIVM_GSAT: the walk's state from the context's W and `select` (pmf_gsat_start); True when a state was made, False
+        when the one at hand belongs to the current W and was kept."""
+        sel = np.ascontiguousarray(select, dtype=np.int32)
+        assert sel.shape == (self.k,), (sel.shape, self.k)
+        started = ctypes.c_int32(0)
+        self._chk(self._lib.pmf_gsat_start(self._h, sel.ctypes.data, 1 if force else 0, ctypes.byref(started)))
+        return bool(started.value)
+
+    def gsat_walk(self, idx):
+        """SIVM_GSAT: the probes `idx` (data columns) in order; per probe the vertex it replaced, -1 rejected, -2 skipped
+        (pmf_gsat_walk)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        out = np.empty(max(idx.shape[0], 1), dtype=np.int32)
+        self._chk(self._lib.pmf_gsat_walk(self._h, idx.ctypes.data, int(idx.shape[0]), out.ctypes.data))
+        return out[:idx.shape[0]]
+
+    def gsat_probe_vec(self, vec):
+        """SIVM_GSAT: online_update_w on a vector of data_dimension values; the vertex it replaced or -1 (pmf_gsat_probe_vec)."""
+        vec = _f32c(vec).reshape(-1)
+        assert vec.shape == (self.m,), (vec.shape, self.m)
+        slot = ctypes.c_int32(-1)
+        self._chk(self._lib.pmf_gsat_probe_vec(self._h, vec.ctypes.data, ctypes.byref(slot)))
+        return int(slot.value)
+
+    def gsat_get_volumes(self):
+        """SIVM_GSAT: (the reference's _v since the start as a float64 array, V) (pmf_gsat_get_volumes)."""
+        count, V = ctypes.c_int64(0), ctypes.c_double(0.0)
+        self._chk(self._lib.pmf_gsat_get_volumes(self._h, None, 0, ctypes.byref(count), ctypes.byref(V)))
+        out = np.empty(max(int(count.value), 1), dtype=np.float64)
+        self._chk(self._lib.pmf_gsat_get_volumes(self._h, out.ctypes.data, int(count.value), ctypes.byref(count), ctypes.byref(V)))
+        return out[:int(count.value)], float(V.value)
+
+    def gsat_get_d(self):
+        """SIVM_GSAT: the reference's D, (num_bases + 1) x (num_bases + 1) float64 (pmf_gsat_get_d)."""
+        D = np.empty((self.k + 1, self.k + 1), dtype=np.float64)
+        self._chk(self._lib.pmf_gsat_get_d(self._h, D.ctypes.data))
+        return D
 
     def greedy_select(self, nsel, transposed=False):
         """GREEDY / GREEDYCUR: `nsel` indices in selection order among the columns of the data, or (transposed) among its rows

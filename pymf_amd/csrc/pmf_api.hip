@@ -40,6 +40,7 @@
 #include "pmf_sivm.h"
 #include "pmf_colsel.h"
 #include "pmf_sgreedy.h"
+#include "pmf_gsat.h"
 #include "pmf_aa.h"
 #include "pmf_svd.h"
 #include "pmf_cur.h"
@@ -62,6 +63,7 @@
 #include "pmf_host_sivm.h"
 #include "pmf_host_colsel.h"
 #include "pmf_host_sgreedy.h"
+#include "pmf_host_gsat.h"
 #include "pmf_host_aa.h"
 #include "pmf_host_svd.h"
 #include "pmf_host_cur.h"
@@ -512,6 +514,47 @@ int pmf_sivm_get_volumes(pmf_ctx* c, double* volumes) {
   if (!c->sv_have_select || !c->sg_have_vol) return fail(c, PMF_EINVAL, "pmf_sivm_get_volumes: no selection yet (update_w has not run)");
   HIPCHK(c, hipSetDevice(c->device));
   return sgreedy_get_volumes(c, volumes);
+}
+
+int pmf_gsat_start(pmf_ctx* c, const int32_t* select, int32_t force, int32_t* started) {
+  if (!c || !select) return fail(c, PMF_EINVAL, "pmf_gsat_start: bad arguments");
+  PMFCHK(gsat_usable(c, "pmf_gsat_start"));
+  PMFCHK(need(c, true, true, false));
+  if (multi_rank(c)) return fail(c, PMF_EINVAL, "pmf_gsat_start: one rank only in this build");
+  if (started) *started = 0;
+  if (c->gs_started && !force) return PMF_OK;
+  PMFCHK(gsat_start(c, select));
+  if (started) *started = 1;
+  return PMF_OK;
+}
+
+int pmf_gsat_walk(pmf_ctx* c, const int64_t* idx, int64_t n, int32_t* slots_out) {
+  if (!c || (n > 0 && (!idx || !slots_out))) return fail(c, PMF_EINVAL, "pmf_gsat_walk: bad arguments");
+  PMFCHK(gsat_usable(c, "pmf_gsat_walk"));
+  PMFCHK(need(c, true, true, false));
+  return gsat_walk(c, idx, n, slots_out);
+}
+
+int pmf_gsat_probe_vec(pmf_ctx* c, const float* vec, int32_t* slot_out) {
+  if (!c || !vec || !slot_out) return fail(c, PMF_EINVAL, "pmf_gsat_probe_vec: bad arguments");
+  PMFCHK(gsat_usable(c, "pmf_gsat_probe_vec"));
+  PMFCHK(need(c, true, true, false));
+  return gsat_probe_vec(c, vec, slot_out);
+}
+
+int pmf_gsat_get_volumes(pmf_ctx* c, double* volumes, int64_t cap, int64_t* count, double* V) {
+  if (!c || cap < 0 || (cap > 0 && !volumes)) return fail(c, PMF_EINVAL, "pmf_gsat_get_volumes: bad arguments");
+  PMFCHK(gsat_ready(c, "pmf_gsat_get_volumes"));
+  if (count) *count = (int64_t)c->gs_log.size();
+  if (V) *V = c->gs_V;
+  std::copy_n(c->gs_log.begin(), std::min<size_t>((size_t)cap, c->gs_log.size()), volumes);
+  return PMF_OK;
+}
+
+int pmf_gsat_get_d(pmf_ctx* c, double* D) {
+  if (!c || !D) return fail(c, PMF_EINVAL, "pmf_gsat_get_d: bad arguments");
+  PMFCHK(need(c, true, true, false));
+  return gsat_get_d(c, D);
 }
 
 int pmf_greedy_select(pmf_ctx* c, int32_t transposed, int32_t nsel, int32_t* select) {
@@ -1178,6 +1221,7 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
     if (name[0] == 's') {
       if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "sivm_rule: 0 (SIVM), 1 (LAESA) or 2 (GMAP)");
       if (value != 0 && c->sv_sgreedy) return fail(c, PMF_EINVAL, "sivm_rule: LAESA and GMAP not together with sivm_sgreedy");
+      if (value != 0 && c->sv_gsat) return fail(c, PMF_EINVAL, "sivm_rule: LAESA and GMAP not together with sivm_gsat");
       c->sv_rule = (int)value;
     } else {
       if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "gmap_method: 0 (pca), 1 (aa) or 2 (nmf)");
@@ -1190,9 +1234,18 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
     if (c->algo != PMF_ALGO_SIVM) return fail(c, PMF_EINVAL, "sivm_sgreedy: SIVM contexts only");
     if (value != 0 && value != 1) return fail(c, PMF_EINVAL, "sivm_sgreedy: 0 or 1");
     if (value == 1 && c->sv_rule != 0) return fail(c, PMF_EINVAL, "sivm_sgreedy: not together with sivm_rule 1 (LAESA) or 2 (GMAP)");
+    if (value == 1 && c->sv_gsat) return fail(c, PMF_EINVAL, "sivm_sgreedy: not together with sivm_gsat");
     if ((int)value != c->sv_sgreedy) c->sg_have_vol = false;
     c->sv_sgreedy = (int)value;
     choose_stat_site(c, false);
+    return PMF_OK;
+  }
+  if (std::strcmp(name, "sivm_gsat") == 0) {
+    if (c->algo != PMF_ALGO_SIVM) return fail(c, PMF_EINVAL, "sivm_gsat: SIVM contexts only");
+    if (value != 0 && value != 1) return fail(c, PMF_EINVAL, "sivm_gsat: 0 or 1");
+    if (value == 1 && (c->sv_rule != 0 || c->sv_sgreedy)) return fail(c, PMF_EINVAL, "sivm_gsat: not together with sivm_rule 1 (LAESA) or 2 (GMAP) or sivm_sgreedy");
+    if ((int)value != c->sv_gsat) c->gs_started = false;
+    c->sv_gsat = (int)value;
     return PMF_OK;
   }
   if (std::strcmp(name, "profile_sivm_rows") == 0) {

@@ -178,6 +178,16 @@ struct pmf_ctx {
   double *dSgM = nullptr, *dSgVol = nullptr;
   int sv_sgreedy = 0;           // pmf_set_option("sivm_sgreedy"): pmf_update_w selects by the exact simplex volume (sv_rule stays 0)
   bool sg_have_vol = false;     // dSgVol holds the volumes of a W step
+  // SIVM_GSAT (pmf_gsat.h): the vertices as rows ([k][m] float32); float64: the distance table [64][64], the last probe's distances
+  // [64], V; per launch the probes' volumes [256] and distances [256][64]; allocated by the first pmf_gsat_start.  On the host
+  // V and the reference's _v since the start ([V at the first swap, the accepted volumes ...])
+  float* dGsW = nullptr;
+  double *dGsTab = nullptr, *dGsProbe = nullptr;
+  int* dGsCtl = nullptr;        // [0] the accepted position of a launch, [1] accepted volumes of the call
+  int sv_gsat = 0;              // pmf_set_option("sivm_gsat"): the W step is pmf_gsat_walk / pmf_gsat_probe_vec, pmf_update_w refuses
+  bool gs_started = false;      // the walk's state belongs to the context's W.  <- W from the caller
+  double gs_V = 0.0;
+  std::vector<double> gs_log;
   int opt_profile_sivm_rows = 0;   // pmf_set_option("profile_sivm_rows"): pmf_profile_enable times the rounds of the long-sample pass (SITE_SIVM_ROWS)
   // AA (pmf_aa.h): W_hat, the points X and residuals R ([mp][KP]); the two partials arrays of the pricing pass ([2][wgs][KP]); per
   // base the corral's Gram matrix, data columns and weights by slot, the finished flag; unfinished bases per round; the
@@ -414,6 +424,7 @@ void v_replaced(pmf_ctx* c) {
 void w_replaced(pmf_ctx* c, bool by_caller) {   // by_caller: uploaded or filled through the ABI (not the NNDSVD init, not a restored snapshot)
   c->have_w = true; c->ps_valid = c->num_valid = c->trace_ready = c->w_implicit = false;
   c->cl_err_valid = false;
+  if (by_caller) c->gs_started = false;           // (SIVM_GSAT: the walk starts again from the caller's vertices)
   if (by_caller) c->cn_user_w = c->algo == PMF_ALGO_CNMF;   // (CNMF: the error is taken against this W until a G step rebinds it)
 }
 // hd_synced, hd_force: what the float64 H (SNMF, CNMF) is to the new float32 H -- written with it (true, false), the caller's float64

@@ -128,6 +128,7 @@ int sgreedy_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, i
 // SIVM_SGREEDY.update_w (sivm_sgreedy.py:96-133) under "sivm_sgreedy":
 // the rounds on the resident V and buffers, then the gather
 int sivm_update_w(pmf_ctx* c) {
+  if (c->sv_gsat) return fail(c, PMF_EINVAL, "SIVM_GSAT: no W step of its own (pmf_gsat_walk and pmf_gsat_probe_vec move the vertices)");
   PMFCHK(sivm_alloc(c));
   const SivmBufs b{c->dSvState, c->dSvPart, c->dSvPartIdx, c->dSvScal, c->dSvSel};
   if (c->sv_sgreedy) PMFCHK(sgreedy_panel_rounds(c, c->dV, c->np, (int)c->m, (int)c->n, c->k, c->sv_metric, c->sv_init == 1, b));
