@@ -108,7 +108,15 @@ const char* pmf_last_error(const pmf_ctx* ctx);   /* ctx may be NULL: last creat
 
 /* V: host row-major m_local x n float32 with leading dimension ld (elements). Copied. */
 int pmf_set_v_dense_f32(pmf_ctx* ctx, const float* V, int64_t ld);
-/* V as CSR (m_local rows): indptr[m_local+1] int64, indices[nnz] int32, vals[nnz] f32. */
+/* V as CSR (m_local rows): indptr[m_local+1] int64, indices[nnz] int32, vals[nnz] f32.  Copied.  Semantics: the dense
+ * algorithm on the matrix these arrays describe (entries of one (row, column) pair add up); pmf_frobenius and
+ * PMF_COMPUTE_ERR refuse CSR data.  SNMF and NMF contexts only; every other family returns PMF_EINVAL.
+ *   SNMF: num_bases > 128, or n * KP * 4 bytes beyond 160 KiB, expands the rows to a dense V on the device.
+ *   NMF:  never a dense V.  The call checks the arrays (indptr from 0 to nnz and not decreasing, indices in [0, n)),
+ *         builds the CSR arrays of V^T on the host by a stable counting sort and uploads them beside the rows; both half
+ *         steps then run one gather-form kernel on stored entries (pmf_path_name: "nmf_csr_gather<NT>"), with the
+ *         same bits on every run.  PMF_EINVAL, the message naming the limit, for num_bases > 128 and for more than
+ *         one rank (nranks > 1, or a host / IPC transport installed).  pmf_stream_* refuses while CSR data is resident. */
 int pmf_set_v_csr_f32(pmf_ctx* ctx, const int64_t* indptr, const int32_t* indices,
                       const float* vals, int64_t nnz);
 /* Fill V on the device with the bench's synthetic U[0,1) stream (counter-based, so

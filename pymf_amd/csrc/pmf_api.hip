@@ -33,6 +33,7 @@
 #include "pmf_nnls_api.h"   // the sub-problem kernels themselves: pmf_nnls_tu.hip
 #include "pmf_inv.h"
 #include "pmf_csr.h"
+#include "pmf_nmf_csr.h"
 #include "pmf_nndsvd.h"
 #include "pmf_topk.h"
 #include "pmf_cnmf.h"
@@ -54,6 +55,7 @@
 #include "pmf_host_nndsvd.h"
 #include "pmf_host_nmf.h"
 #include "pmf_host_snmf.h"
+#include "pmf_host_nmf_csr.h"
 #include "pmf_host_nmfals.h"
 #include "pmf_host_transport.h"
 #include "pmf_host_profile.h"
@@ -275,6 +277,7 @@ static int set_v_dense(pmf_ctx* c, const void* V, bool f64, int64_t ld, const ch
              : upload_rows(c, c->dV, c->np, static_cast<const float*>(V), ld, c->m, c->n));
   PMFCHK(rnmf_data_change_end(c));
   c->have_v = true; c->v_csr = false; c->csr_dense = false; v_replaced(c);
+  nmf_csr_left(c);
   PMFCHK(local_vnorm(c));
   return PMF_OK;
 }
@@ -285,7 +288,8 @@ int pmf_set_v_csr_f32(pmf_ctx* c, const int64_t* indptr, const int32_t* indices,
                       int64_t nnz) {
   if (!c || !indptr || (nnz > 0 && (!indices || !vals)) || nnz < 0)
     return fail(c, PMF_EINVAL, "pmf_set_v_csr_f32: bad arguments");
-  if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF");
+  if (c->algo == PMF_ALGO_NMF) return nmf_csr_set_v(c, indptr, indices, vals, nnz);
+  if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF and NMF");
   HIPCHK(c, hipSetDevice(c->device));
   PMFCHK(dgrow(c, &c->dIndptr, (size_t)c->mp + 1));
   PMFCHK(dgrow(c, &c->dIndices, (size_t)nnz));
@@ -331,6 +335,7 @@ int pmf_fill_v_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   PMFCHK(fill(c, c->dV, c->np, c->m, c->n, row0, seed));
   PMFCHK(rnmf_data_change_end(c));
   c->have_v = true; c->v_csr = false; c->csr_dense = false; v_replaced(c);
+  nmf_csr_left(c);
   PMFCHK(local_vnorm(c));
   return PMF_OK;
 }
@@ -401,6 +406,7 @@ int pmf_set_h_f64(pmf_ctx* c, const double* H) {
 int pmf_get_h_f64(pmf_ctx* c, double* H) {
   PMFCHK(need(c, false, false, true));
   if (!H) return fail(c, PMF_EINVAL, "H is NULL");
+  PMFCHK(nmf_csr_sync_h(c));
   if (h_in_f64(c) && c->dHd) {     // SNMF: the float64 H the device iterates on (entries another writer of the float32 H replaced: widened)
     PMFCHK(ensure_hd(c));
     const size_t bytes = (size_t)c->k * c->n * sizeof(double);
@@ -431,6 +437,7 @@ int pmf_set_h_f32(pmf_ctx* c, const float* H) {
 int pmf_get_h_f32(pmf_ctx* c, float* H) {
   PMFCHK(need(c, false, false, true));
   if (!H) return fail(c, PMF_EINVAL, "H is NULL");
+  PMFCHK(nmf_csr_sync_h(c));
   return download_padded(c, H, c->n, c->dH, c->np, c->k, c->n);
 }
 
@@ -445,6 +452,7 @@ static int run_step(pmf_ctx* c, bool w_step) {
   PMFCHK(need(c, r.v, r.w, r.h));
   if (c->v_csr && (w_step ? a.dense_w : a.dense_h)) return fail(c, PMF_EINVAL, std::string(a.family) + ": dense data only");
   PMFCHK(step(c));
+  PMFCHK(nmf_csr_sync_h(c));                     // (NMF on CSR data: dH follows the working copy H^T before the call returns)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (!a.nmf_family) return PMF_OK;
   PMFCHK(ipc_check(c));                          // the NMF family: the exchange's verdict, and the inverse's behind a W step
@@ -710,6 +718,7 @@ int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (!c) return PMF_EINVAL;
   if (!algo_row(c).streamable)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
+  if (nmf_csr(c)) return fail(c, PMF_EINVAL, "pmf_stream_*: not on an NMF context that holds CSR data (set dense data, or none, first)");
   if (!c->have_w || !c->have_h) return fail(c, PMF_EINVAL, "pmf_stream_begin: W and H must be set");
   if (max_tile_rows < 1) return fail(c, PMF_EINVAL, "pmf_stream_begin: max_tile_rows must be >= 1");
   HIPCHK(c, hipSetDevice(c->device));

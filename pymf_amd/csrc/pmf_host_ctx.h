@@ -94,6 +94,15 @@ struct pmf_ctx {
   int64_t* dIndptr = nullptr; int32_t* dIndices = nullptr; float* dVals = nullptr; int64_t nnz = 0;
   bool v_csr = false;
   bool csr_dense = false;       // CSR data with num_bases > 128: a dense image in dV serves the data paths (no CSR kernel at that width)
+  // NMF on CSR data (pmf_nmf_csr.h, pmf_host_nmf_csr.h): the CSR arrays of V^T (built on the host by pmf_set_v_csr_f32), the working
+  // copy H^T [np][KP], S = W^T W [KP][KP] (the G of the H step), the workgroups' slabs of k_nmf_sp_step
+  int64_t* dTIndptr = nullptr; int32_t* dTIndices = nullptr; float* dTVals = nullptr;
+  float *dHT = nullptr, *dSw = nullptr, *dSpSlab = nullptr;
+  int sp_wgs_cap = 0;           // slabs dSpSlab holds
+  bool ht_valid = false;        // dHT = dH^T.  <- H
+  bool ht_newer = false;        // an H step wrote dHT and dH has not followed yet (nmf_csr_sync_h).  <- H
+  bool sw_valid = false;        // dSw = W^T W of the current W.  <- W
+  std::string path_dense;       // pmf_path_name of the context with dense data (CSR data on an NMF context: "nmf_csr_gather")
   int* dSing = nullptr;         // SNMF: raised by the inverse kernels when H H^T has a zero pivot (check_singular)
   double* dQp = nullptr;        // k_nnqp_big (NMFALS, num_bases > 64): per-workgroup inverse images
   double* dBinv = nullptr;      // k_nnqp_quad: B = inv(HA), [KP][KP] float64
@@ -306,6 +315,8 @@ int nmf_fused_pass(pmf_ctx* c);
 int snmf_fused_pass(pmf_ctx* c);
 int snmf_inverse(pmf_ctx* c);
 int ensure_ps(pmf_ctx* c);
+int nmf_csr_sync_h(pmf_ctx* c);
+void choose_stat_site(pmf_ctx* c, bool gram);
 
 // ---- device memory: every buffer of a context is allocated, grown and released here ----------
 // (the IPC receive area alone lives outside c->owned: it is allocated for export and peers hold handles to it)
@@ -356,8 +367,10 @@ int dgrow(pmf_ctx* c, T** p, int64_t* cap, int64_t count, size_t per = 1, bool s
   return PMF_OK;
 }
 
-// CSR kernels serve the data paths (SNMF, num_bases <= 128); wider contexts keep a dense image of the CSR rows
+// CSR kernels serve the data paths (SNMF and NMF, num_bases <= 128); wider SNMF contexts keep a dense image of the CSR rows
 static inline bool use_csr(const pmf_ctx* c) { return c->v_csr && !c->csr_dense; }
+// NMF on CSR data: both half steps are k_nmf_sp_step (pmf_host_nmf_csr.h)
+static inline bool nmf_csr(const pmf_ctx* c) { return c->algo == PMF_ALGO_NMF && use_csr(c); }
 
 int ensure_dv(pmf_ctx* c) {
   if (c->dV) return PMF_OK;
@@ -423,6 +436,7 @@ void v_replaced(pmf_ctx* c) {
 }
 void w_replaced(pmf_ctx* c, bool by_caller) {   // by_caller: uploaded or filled through the ABI (not the NNDSVD init, not a restored snapshot)
   c->have_w = true; c->ps_valid = c->num_valid = c->trace_ready = c->w_implicit = false;
+  c->sw_valid = false;
   c->cl_err_valid = false;
   if (by_caller) c->gs_started = false;           // (SIVM_GSAT: the walk starts again from the caller's vertices)
   if (by_caller) c->cn_user_w = c->algo == PMF_ALGO_CNMF;   // (CNMF: the error is taken against this W until a G step rebinds it)
@@ -432,6 +446,7 @@ void w_replaced(pmf_ctx* c, bool by_caller) {   // by_caller: uploaded or filled
 void h_replaced(pmf_ctx* c, bool hd_synced, bool hd_force) {
   c->have_h = true; c->g_valid = c->num_valid = c->trace_ready = false; c->g_parts = 0; c->hd_synced = hd_synced; c->hd_force = hd_force;
   c->cl_err_valid = false;
+  c->ht_valid = c->ht_newer = false;
   if (c->algo == PMF_ALGO_CMEANS) c->cl_sums_valid = false;   // (Kmeans' sums follow the assignment, not H: kmeans.py:82-87)
 }
 void g_replaced(pmf_ctx* c) {        // CNMF

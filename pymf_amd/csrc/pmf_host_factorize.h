@@ -118,6 +118,7 @@ struct NmfLoopSteps {
 
   int close(pmf_ctx* c) {
     c->want_trace = c->fixed_h_loop = c->gram_partial_ok = false;
+    PMFCHK(nmf_csr_sync_h(c));   // NMF on CSR data: dH follows the working copy H^T
     return materialize_w(c);     // Gram-space SNMF loop: W = V M once
   }
 };

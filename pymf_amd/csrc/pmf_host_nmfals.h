@@ -144,6 +144,7 @@ int do_update_w(pmf_ctx* c) {
   c->ps_valid = false;
   c->psd_fresh = false;
   c->trace_ready = false;
+  if (nmf_csr(c)) return nmf_csr_update_w(c);
   switch (c->algo) {
     case PMF_ALGO_NMF: return nmf_update_w(c);
     case PMF_ALGO_BNMF: return nmf_update_w(c);
@@ -155,6 +156,7 @@ int do_update_w(pmf_ctx* c) {
 }
 
 int do_update_h(pmf_ctx* c) {
+  if (nmf_csr(c)) return nmf_csr_update_h(c);
   switch (c->algo) {
     case PMF_ALGO_NMF: return nmf_update_h(c);
     case PMF_ALGO_BNMF: return nmf_update_h(c);

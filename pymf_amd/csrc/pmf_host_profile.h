@@ -107,6 +107,14 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.flops = 4.0 * nnz * k + 4.0 * m * k * k;                  // SURVEY: SpMM, (.) inv, W^T V, W^T W
     st.exec_flops = 4.0 * nnz * k + m * k * (k + 16.0);          // V M, W^T V, upper triangle of W^T W
     st.bytes = 4.0 * m * k + 8.0 * nnz + 8.0 * (m + 1.0);
+  } else if (nmf_csr(c)) {
+    st.site = SITE_CSR_PASS;                      // both half steps of an iteration, alternating; the figures are the W step's
+    snprintf(buf, sizeof(buf), "k_nmf_sp_step<%d>", c->NT);
+    st.name = buf;
+    const double kp = (double)c->KP;
+    st.flops = 2.0 * nnz * k + 4.0 * m * k * k;                  // the gather, X G, X^T X
+    st.exec_flops = 2.0 * nnz * kp + 2.0 * m * kp * kp + m * kp * (kp + 16.0);
+    st.bytes = 12.0 * nnz + 8.0 * m * kp + 4.0 * nnz * kp;       // CSR arrays once, X read and written, the gathered rows of Y
   } else if (c->fused_wgs > 0 && c->algo != PMF_ALGO_NMFALS) {
     st.site = SITE_FUSED;
     st.name = c->fused8 ? c->path.c_str()

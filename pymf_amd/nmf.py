@@ -162,6 +162,11 @@ class NMF(object):
     #: k = 64).  The same test spares the digest of an array that was not handed out since it was last
     #: made equal to the device copy.  True: refresh after every call, digest before every call.
     eager_factors = False
+    #: True: `data` may be a scipy.sparse matrix (NMF itself and subclasses that keep its update rule -- not BNMF, RNMF, NMFALS,
+    #: NMFNNLS, CNMF ...).  The reference fails on sparse data (UFuncTypeError at nmf.py:131), so the default refuses it with
+    #: TypeError; with the flag the semantics are dense NMF on data.toarray(), computed from the stored entries alone
+    #:: one rank, num_bases <= 128, no error norm (frobenius_norm() keeps the reference's -123456).
+    accept_sparse = False
 
     def __init__(self, data, num_bases=4):
         self._logger = logging.getLogger("pymf")               # nmf.py:73-90
@@ -300,9 +305,25 @@ class NMF(object):
                           "reference would compute in float64, nmf.py:122-132) -- tolerances: DESIGN.md section 4"
                           % type(self).__name__, PrecisionWarning, stacklevel=6)
 
+    def _sparse_nmf(self):
+        """`data` is a scipy.sparse matrix and this object takes it (accept_sparse, NMF's own update rule)."""
+        return bool(self.accept_sparse) and self._ALGO == _lib.ALGO_NMF and _is_sparse(self.data)
+
     def _upload_sparse(self, ctx):
-        raise TypeError("scipy.sparse data is not supported by %s (the reference fails "
-                        "with UFuncTypeError at nmf.py:131)" % type(self).__name__)
+        if not self._sparse_nmf():
+            raise TypeError("scipy.sparse data is not supported by %s (the reference fails "
+                            "with UFuncTypeError at nmf.py:131)" % type(self).__name__)
+        if self._world().size > 1:
+            raise NotImplementedError("NMF on scipy.sparse data: one rank only in this build")
+        if self._num_bases > 128:
+            raise ValueError("NMF on scipy.sparse data: num_bases > 128 is not supported by this build")
+        csr = self.data.tocsr()
+        self._warn_if_float64(csr.data)
+        if not csr.has_canonical_format:
+            if csr is self.data:
+                csr = csr.copy()                                # (the caller's matrix keeps its entries as they are)
+            csr.sum_duplicates()
+        ctx.set_v_csr(csr.indptr, csr.indices, csr.data)
 
     def _stream_rows(self):
         """Tile height of the streamed mode (rounded to 64 rows), or 0 when `data` is kept resident."""
@@ -536,6 +557,12 @@ class NMF(object):
     def factorize(self, niter=1, show_progress=False,
                   compute_w=True, compute_h=True, compute_err=True):
         """Factorize s.t. WH = data (nmf.py:141-202)."""
+        if compute_err and self._sparse_nmf():
+            # reference: frobenius_norm() returns -123456 for sparse data (nmf.py:109-112),
+            # so ferr is a constant and the loop "converges" at i == 2 (nmf.py:198-202).
+            raise TypeError("compute_err=True on scipy.sparse data: the reference's "
+                            "frobenius_norm() only returns its -123456 sentinel there; "
+                            "pass compute_err=False")
         self._logger.setLevel(logging.INFO if show_progress else logging.ERROR)   # nmf.py:166-169
         t_call = time.perf_counter()
         self.last_call_ms = {}
