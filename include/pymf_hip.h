@@ -119,6 +119,24 @@ int pmf_set_v_dense_f32(pmf_ctx* ctx, const float* V, int64_t ld);
  *         one rank (nranks > 1, or a host / IPC transport installed).  pmf_stream_* refuses while CSR data is resident. */
 int pmf_set_v_csr_f32(pmf_ctx* ctx, const int64_t* indptr, const int32_t* indices,
                       const float* vals, int64_t nnz);
+/* V as CSC (n columns): indptr[n+1] int64, indices[nnz] int32 (row ids, ascending within a column, no duplicates), vals[nnz]
+ * f32.  Copied.  SIVM contexts (algo 10) under "sivm_rule" 0 (SIVM) or 1 (LAESA) only -- the reference's own sparse branch
+ * (pymf/sivm.py:110-120, pymf/dist.py:37-42); every other context, and a SIVM context under "sivm_rule" 2, "sivm_sgreedy" or
+ * "sivm_gsat", returns PMF_EINVAL.  So does malformed input, checked on the host before anything is uploaded: indptr not from
+ * 0 to nnz or decreasing, a row id outside [0, m), unsorted or duplicate rows in a column.  Semantics: the dense algorithm on
+ * the matrix the arrays describe (stored zeros are entries like any other), computed from the stored entries alone: no dense V
+ * exists on the device (a CSC upload releases one, a dense upload releases the CSC arrays).  pmf_update_w runs
+ * k_sivm_csc_pass (pmf_sivm_csc.h; pmf_path_name: "sivm_csc_teams<TEAM>", TEAM the lanes per column of the next W step), pmf_update_h forms W^T V from the stored entries and
+ * then runs the dense H step; H and W are dense.  A column measured against itself has distance exactly 0 under l2 and l1, as
+ * on dense data.  While CSC data is resident pmf_frobenius, PMF_COMPUTE_ERR, pmf_sivm_select, pmf_gsat_* and a W step under a
+ * rule other than SIVM or LAESA refuse (PMF_EINVAL, with a message); pmf_stream_* refuses SIVM contexts anyway.
+ * pmf_set_option "sivm_csc_team" (0 default: by the mean stored entries per column; 4, 16, 64) forces the lanes that share a
+ * column in k_sivm_csc_pass: the summation order, and so the last bits of a distance, depend on it and on nothing else.
+ * pmf_check_csc: the same check of the arrays alone, for an m x n matrix, without a context or a device (the message through
+ * pmf_last_error(NULL)). */
+int pmf_set_v_csc_f32(pmf_ctx* ctx, const int64_t* indptr, const int32_t* indices,
+                      const float* vals, int64_t nnz);
+int pmf_check_csc(int64_t m, int64_t n, const int64_t* indptr, const int32_t* indices, int64_t nnz);
 /* Fill V on the device with the bench's synthetic U[0,1) stream (counter-based, so
  * the values depend only on (seed, global row, column)); row0 = first global row. */
 int pmf_fill_v_uniform(pmf_ctx* ctx, uint64_t seed, int64_t row0);

@@ -40,6 +40,8 @@ SYMBOLS = [
     ("pmf_set_v_dense_f32", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64]),
     ("pmf_set_v_dense_f64", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64]),
     ("pmf_set_v_csr_f32", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64]),
+    ("pmf_set_v_csc_f32", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64]),
+    ("pmf_check_csc", _c.c_int, [_c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("pmf_fill_v_uniform", _c.c_int, [_ctx, _c.c_uint64, _c.c_int64]),
     ("pmf_set_w_f32", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_get_w_f32", _c.c_int, [_ctx, _c.c_void_p]),
@@ -186,6 +188,16 @@ def _f32c(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def check_csc(m, n, indptr, indices):
+    """pmf_check_csc: raises PmfError (code PMF_EINVAL) unless the arrays are the CSC image of an m x n matrix as
+    pmf_set_v_csc_f32 takes it.  Runs on the host alone."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    if indptr.shape[0] != n + 1:
+        raise ValueError("indptr must have n + 1 entries")
+    check(load().pmf_check_csc(m, n, indptr.ctypes.data, indices.ctypes.data, int(indices.shape[0])))
+
+
 class Context(object):
     """Thin owner of one pmf_ctx*."""
 
@@ -231,6 +243,14 @@ class Context(object):
         vals = _f32c(vals)
         assert indptr.shape[0] == self.m + 1
         self._chk(self._lib.pmf_set_v_csr_f32(self._h, indptr.ctypes.data, indices.ctypes.data,
+                                              vals.ctypes.data, int(vals.shape[0])))
+
+    def set_v_csc(self, indptr, indices, vals):
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        vals = _f32c(vals)
+        assert indptr.shape[0] == self.n + 1 and indices.shape[0] == vals.shape[0]
+        self._chk(self._lib.pmf_set_v_csc_f32(self._h, indptr.ctypes.data, indices.ctypes.data,
                                               vals.ctypes.data, int(vals.shape[0])))
 
     def fill_v_uniform(self, seed, row0=0):

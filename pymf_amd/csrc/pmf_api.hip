@@ -40,6 +40,7 @@
 #include "pmf_cluster.h"
 #include "pmf_sivm.h"
 #include "pmf_colsel.h"
+#include "pmf_sivm_csc.h"
 #include "pmf_sgreedy.h"
 #include "pmf_gsat.h"
 #include "pmf_aa.h"
@@ -64,6 +65,7 @@
 #include "pmf_host_cluster.h"
 #include "pmf_host_sivm.h"
 #include "pmf_host_colsel.h"
+#include "pmf_host_sivm_csc.h"
 #include "pmf_host_sgreedy.h"
 #include "pmf_host_gsat.h"
 #include "pmf_host_aa.h"
@@ -271,6 +273,7 @@ static int rnmf_data_change_end(pmf_ctx* c) {
 static int set_v_dense(pmf_ctx* c, const void* V, bool f64, int64_t ld, const char* who) {
   if (!c || !V || ld < c->n) return fail(c, PMF_EINVAL, std::string(who) + ": bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
+  PMFCHK(sivm_csc_left(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
   PMFCHK(f64 ? upload_rows(c, c->dV, c->np, static_cast<const double*>(V), ld, c->m, c->n)
@@ -318,6 +321,17 @@ int pmf_set_v_csr_f32(pmf_ctx* c, const int64_t* indptr, const int32_t* indices,
   return PMF_OK;
 }
 
+int pmf_set_v_csc_f32(pmf_ctx* c, const int64_t* indptr, const int32_t* indices, const float* vals, int64_t nnz) {
+  if (!c || !indptr || (nnz > 0 && (!indices || !vals)) || nnz < 0) return fail(c, PMF_EINVAL, "pmf_set_v_csc_f32: bad arguments");
+  return sivm_csc_set_v(c, indptr, indices, vals, nnz);
+}
+
+int pmf_check_csc(int64_t m, int64_t n, const int64_t* indptr, const int32_t* indices, int64_t nnz) {
+  if (m < 1 || n < 1 || !indptr || (nnz > 0 && !indices) || nnz < 0) return fail(nullptr, PMF_EINVAL, "pmf_check_csc: bad arguments");
+  if (const char* why = csc_check(m, n, indptr, indices, nnz)) return fail(nullptr, PMF_EINVAL, std::string("pmf_check_csc: ") + why);
+  return PMF_OK;
+}
+
 static int fill(pmf_ctx* c, float* X, int64_t ld, int64_t rows, int64_t cols, int64_t row0, uint64_t seed) {
   HIPCHK(c, hipSetDevice(c->device));
   const int64_t E = rows * cols;
@@ -330,6 +344,7 @@ static int fill(pmf_ctx* c, float* X, int64_t ld, int64_t rows, int64_t cols, in
 
 int pmf_fill_v_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   if (!c) return PMF_EINVAL;
+  PMFCHK(sivm_csc_left(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
   PMFCHK(fill(c, c->dV, c->np, c->m, c->n, row0, seed));
@@ -475,6 +490,7 @@ int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, do
   const Operands r = a.loop_reads(cw, ch);
   PMFCHK(need(c, r.v, r.w, r.h));
   if (niter < 0 || (ce && !ferr)) return fail(c, PMF_EINVAL, "pmf_factorize: bad arguments");
+  if (ce && c->v_csc) return fail(c, PMF_EINVAL, "PMF_COMPUTE_ERR on CSC data: the reference's frobenius_norm returns its -123456 sentinel there (nmf.py:109-112)");
   if (iters_done) *iters_done = 0;
   if (converged_at) *converged_at = -1;
   if (c->algo == PMF_ALGO_CNMF) {
@@ -1237,6 +1253,13 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
       c->sv_gmap_method = (int)value;
     }
     choose_stat_site(c, false);
+    return PMF_OK;
+  }
+  if (std::strcmp(name, "sivm_csc_team") == 0) {
+    if (c->algo != PMF_ALGO_SIVM) return fail(c, PMF_EINVAL, "sivm_csc_team: SIVM contexts only");
+    if (value != 0 && value != 4 && value != 16 && value != 64) return fail(c, PMF_EINVAL, "sivm_csc_team: 0 (by the mean column length), 4, 16 or 64");
+    c->opt_sivm_csc_team = (int)value;
+    if (c->v_csc) sivm_csc_name_path(c);
     return PMF_OK;
   }
   if (std::strcmp(name, "sivm_sgreedy") == 0) {

@@ -93,6 +93,8 @@ struct pmf_ctx {
   // CSR V (SNMF sparse path)
   int64_t* dIndptr = nullptr; int32_t* dIndices = nullptr; float* dVals = nullptr; int64_t nnz = 0;
   bool v_csr = false;
+  bool v_csc = false;           // SIVM / LAESA on CSC data (pmf_set_v_csc_f32): the three arrays above hold the COLUMNS of V (indptr [np + 1]), dV is released
+  int opt_sivm_csc_team = 0;    // pmf_set_option("sivm_csc_team"): 0 by the mean column length, or 4, 16, 64 lanes per column in k_sivm_csc_pass
   bool csr_dense = false;       // CSR data with num_bases > 128: a dense image in dV serves the data paths (no CSR kernel at that width)
   // NMF on CSR data (pmf_nmf_csr.h, pmf_host_nmf_csr.h): the CSR arrays of V^T (built on the host by pmf_set_v_csr_f32), the working
   // copy H^T [np][KP], S = W^T W [KP][KP] (the G of the H step), the workgroups' slabs of k_nmf_sp_step

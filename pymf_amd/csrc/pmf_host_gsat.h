@@ -34,7 +34,7 @@ int gsat_usable(pmf_ctx* c, const char* who) {
 
 // the walk's state from the context's W and the caller's `select`: the image, the table, V = cmdet(D) (sivm_gsat.py:84-88)
 int gsat_start(pmf_ctx* c, const int32_t* select) {
-  if (c->v_csr || !c->dV) return fail(c, PMF_EINVAL, "pmf_gsat_start: dense resident data only");
+  if (c->v_csr || c->v_csc || !c->dV) return fail(c, PMF_EINVAL, "pmf_gsat_start: dense resident data only");
   PMFCHK(gsat_alloc(c));
   c->gs_started = false;
   HIPCHK(c, hipMemcpyAsync(c->dSvSel, select, (size_t)c->k * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));

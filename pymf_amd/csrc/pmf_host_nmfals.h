@@ -170,6 +170,7 @@ int do_update_h(pmf_ctx* c) {
 int frobenius_direct(pmf_ctx* c, double* out) {
   PMFCHK(materialize_w(c));
   if (c->v_csr) return fail(c, PMF_EINVAL, "frobenius on CSR data: the reference returns its -123456 sentinel (nmf.py:109-112)");
+  if (c->v_csc) return fail(c, PMF_EINVAL, "frobenius on CSC data: the reference returns its -123456 sentinel (nmf.py:109-112)");
   const int nb = (int)(c->mp / 64);
   PMFCHK(launch_resid(c, false, 0.f));
   hipLaunchKernelGGL(k_sum_f64, dim3(1), dim3(256), 0, c->stream, c->dPart, c->resid_parts, c->dScal);

@@ -121,6 +121,9 @@ int gather_selected_w(pmf_ctx* c) {
 // the round drivers of the other two rules of a SIVM context (pmf_host_colsel.h)
 int laesa_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, const SivmBufs& b);
 int gmap_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int method, const SivmBufs& b);
+// ... of SIVM and LAESA on CSC data (pmf_host_sivm_csc.h)
+int sivm_csc_update_w(pmf_ctx* c);
+int sivm_csc_wtv(pmf_ctx* c);
 // ... and of SIVM_SGREEDY (pmf_host_sgreedy.h)
 int sgreedy_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, int nsel, int metric, bool origin, const SivmBufs& b);
 
@@ -128,6 +131,7 @@ int sgreedy_panel_rounds(pmf_ctx* c, const float* A, int64_t ld, int R, int C, i
 // SIVM_SGREEDY.update_w (sivm_sgreedy.py:96-133) under "sivm_sgreedy":
 // the rounds on the resident V and buffers, then the gather
 int sivm_update_w(pmf_ctx* c) {
+  if (c->v_csc) return sivm_csc_update_w(c);
   if (c->sv_gsat) return fail(c, PMF_EINVAL, "SIVM_GSAT: no W step of its own (pmf_gsat_walk and pmf_gsat_probe_vec move the vertices)");
   PMFCHK(sivm_alloc(c));
   const SivmBufs b{c->dSvState, c->dSvPart, c->dSvPartIdx, c->dSvScal, c->dSvSel};
@@ -231,7 +235,7 @@ int sivm_select(pmf_ctx* c, bool trans, int nsel, int metric, bool origin, int p
 
 // pmf_sivm_select: the arguments checked before anything is touched, the selection, read back
 int sivm_select_host(pmf_ctx* c, bool trans, int nsel, int metric, int init, int path, int32_t* select) {
-  if (c->v_csr || !c->dV) return fail(c, PMF_EINVAL, "pmf_sivm_select: dense resident data only");
+  if (c->v_csr || c->v_csc || !c->dV) return fail(c, PMF_EINVAL, "pmf_sivm_select: dense resident data only");
   if (multi_rank(c)) return fail(c, PMF_EINVAL, "pmf_sivm_select: one rank only in this build");
   if (nsel < 1 || nsel > 64) return fail(c, PMF_EINVAL, "pmf_sivm_select: 1 <= nsel <= 64");
   if (metric < 0 || metric > 2) return fail(c, PMF_EINVAL, "pmf_sivm_select: metric 0 (l2), 1 (l1) or 2 (cosine)");
@@ -252,7 +256,8 @@ int sivm_select_host(pmf_ctx* c, bool trans, int nsel, int metric, int init, int
 
 // AA.update_h (aa.py:93-111): one simplex-constrained QP per column, as rounds of non-negative QPs (pmf_sivm.h)
 int sivm_update_h(pmf_ctx* c) {
-  PMFCHK(ensure_ps(c));                          // dPS = (W^T V | W^T W), float32
+  if (c->v_csc) PMFCHK(sivm_csc_wtv(c));         // dPS = (W^T V | ...) from the stored entries
+  else PMFCHK(ensure_ps(c));                     // dPS = (W^T V | W^T W), float32
   if (!c->dSvF) {
     PMFCHK(dalloc(c, &c->dSvF, (size_t)c->KP * c->np));
     PMFCHK(dalloc(c, &c->dSvLam, (size_t)6 * c->np));

@@ -41,6 +41,7 @@ class GMAP(SIVM):
     >>> gmap_mdl.W = np.array([[1.0, 0.0], [0.0, 1.0]])
     >>> gmap_mdl.factorize(compute_w=False)
     """
+    _TAKES_SPARSE = False                                      # (SIVM's and LAESA's rule alone run on CSC data: DESIGN.md 3.23)
 
     def __init__(self, data, num_bases=4, method='pca', robust_map=True):
         SIVM.__init__(self, data, num_bases=num_bases)

@@ -9,7 +9,8 @@ select[0] twice and takes the minimum of the two equal vectors; the device runs 
 
 Everything else is SIVM's: the constructor, `select` in selection order with -1 first under init='origin' (that column of W
 is the LAST data column), W as data columns in the data's dtype, the float64 H, one iteration per factorize(), and the
-limits -- dense resident data, one rank, num_bases <= 64, data_dimension <= 16384, dist_measure 'l2', 'l1' or 'cosine'.
+limits -- dense resident data (scipy.sparse data raises TypeError here, as before; the device pass for LAESA's rule on CSC data
+exists and is reached through the C ABI: DESIGN.md 3.23), one rank, num_bases <= 64, data_dimension <= 16384, dist_measure 'l2', 'l1' or 'cosine'.
 """
 from .sivm import SIVM
 
@@ -31,6 +32,7 @@ class LAESA(SIVM):
     >>> laesa_mdl.W = np.array([[1.0, 0.0], [0.0, 1.0]])
     >>> laesa_mdl.factorize(niter=1, compute_w=False)
     """
+    _TAKES_SPARSE = False                                      # (the class keeps its refusal; DESIGN.md 3.23)
 
     def _context(self):
         fresh = self._ctx is None

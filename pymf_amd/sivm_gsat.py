@@ -52,6 +52,7 @@ class SIVM_GSAT(SIVM):
     """
     _SHIPPED = True
     _NITER = None                                              # any number of iterations (sivm_gsat.py:168)
+    _TAKES_SPARSE = False                                      # (SIVM's and LAESA's rule alone run on CSC data: DESIGN.md 3.23)
 
     def _check_supported(self):
         SIVM._check_supported(self)

@@ -50,6 +50,7 @@ class SIVM_SGREEDY(SIVM):
     >>> sivm_mdl.W = np.array([[1.0, 0.0], [0.0, 1.0]])
     >>> sivm_mdl.factorize(compute_w=False)
     """
+    _TAKES_SPARSE = False                                      # (SIVM's and LAESA's rule alone run on CSC data: DESIGN.md 3.23)
 
     def _context(self):
         fresh = self._ctx is None
