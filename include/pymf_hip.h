@@ -111,14 +111,18 @@ int pmf_set_v_dense_f32(pmf_ctx* ctx, const float* V, int64_t ld);
 /* V as CSR (m_local rows): indptr[m_local+1] int64, indices[nnz] int32, vals[nnz] f32.  Copied.  Semantics: the dense
  * algorithm on the matrix these arrays describe (entries of one (row, column) pair add up); pmf_frobenius and
  * PMF_COMPUTE_ERR refuse CSR data.  SNMF and NMF contexts only; every other family returns PMF_EINVAL.
+ * Both check the arrays on the host before anything is uploaded (indptr from 0 to nnz and not decreasing, indices in
+ * [0, n); the entries of a row may come in any order and repeat): malformed input is PMF_EINVAL and leaves the resident data
+ * as it was.  pmf_check_csr: the same check of the arrays alone, for an m x n matrix, without a context or a device (the
+ * message through pmf_last_error(NULL)).
  *   SNMF: num_bases > 128, or n * KP * 4 bytes beyond 160 KiB, expands the rows to a dense V on the device.
- *   NMF:  never a dense V.  The call checks the arrays (indptr from 0 to nnz and not decreasing, indices in [0, n)),
- *         builds the CSR arrays of V^T on the host by a stable counting sort and uploads them beside the rows; both half
+ *   NMF:  never a dense V.  The call builds the CSR arrays of V^T on the host by a stable counting sort and uploads them beside the rows; both half
  *         steps then run one gather-form kernel on stored entries (pmf_path_name: "nmf_csr_gather<NT>"), with the
  *         same bits on every run.  PMF_EINVAL, the message naming the limit, for num_bases > 128 and for more than
  *         one rank (nranks > 1, or a host / IPC transport installed).  pmf_stream_* refuses while CSR data is resident. */
 int pmf_set_v_csr_f32(pmf_ctx* ctx, const int64_t* indptr, const int32_t* indices,
                       const float* vals, int64_t nnz);
+int pmf_check_csr(int64_t m, int64_t n, const int64_t* indptr, const int32_t* indices, int64_t nnz);
 /* V as CSC (n columns): indptr[n+1] int64, indices[nnz] int32 (row ids, ascending within a column, no duplicates), vals[nnz]
  * f32.  Copied.  SIVM contexts (algo 10) under "sivm_rule" 0 (SIVM) or 1 (LAESA) only -- the reference's own sparse branch
  * (pymf/sivm.py:110-120, pymf/dist.py:37-42); every other context, and a SIVM context under "sivm_rule" 2, "sivm_sgreedy" or

@@ -18,7 +18,7 @@ def snmf_update_h(V, W, H):
     def neg(m):
         return (np.abs(m) - m) / 2.0        # :76-77
 
-    XW = np.dot(V.T, W)                     # :79
+    XW = V.T.dot(W)                         # :79 (np.dot for an ndarray; a scipy.sparse V gives the same product from its entries)
     WW = np.dot(W.T, W)                     # :81
     WW_pos = pos(WW)                        # :82
     WW_neg = neg(WW)                        # :83

@@ -40,6 +40,7 @@ SYMBOLS = [
     ("pmf_set_v_dense_f32", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64]),
     ("pmf_set_v_dense_f64", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64]),
     ("pmf_set_v_csr_f32", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64]),
+    ("pmf_check_csr", _c.c_int, [_c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("pmf_set_v_csc_f32", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("pmf_check_csc", _c.c_int, [_c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64]),
     ("pmf_fill_v_uniform", _c.c_int, [_ctx, _c.c_uint64, _c.c_int64]),
@@ -196,6 +197,16 @@ def check_csc(m, n, indptr, indices):
     if indptr.shape[0] != n + 1:
         raise ValueError("indptr must have n + 1 entries")
     check(load().pmf_check_csc(m, n, indptr.ctypes.data, indices.ctypes.data, int(indices.shape[0])))
+
+
+def check_csr(m, n, indptr, indices):
+    """pmf_check_csr: raises PmfError (code PMF_EINVAL) unless the arrays are the CSR image of an m x n matrix as
+    pmf_set_v_csr_f32 takes it (unsorted rows and repeated entries are fine).  Runs on the host alone."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    if indptr.shape[0] != m + 1:
+        raise ValueError("indptr must have m + 1 entries")
+    check(load().pmf_check_csr(m, n, indptr.ctypes.data, indices.ctypes.data, int(indices.shape[0])))
 
 
 class Context(object):

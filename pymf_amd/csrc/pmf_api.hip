@@ -293,6 +293,8 @@ int pmf_set_v_csr_f32(pmf_ctx* c, const int64_t* indptr, const int32_t* indices,
     return fail(c, PMF_EINVAL, "pmf_set_v_csr_f32: bad arguments");
   if (c->algo == PMF_ALGO_NMF) return nmf_csr_set_v(c, indptr, indices, vals, nnz);
   if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF and NMF");
+  // refused arrays never reach the device: what is resident stays as it was
+  if (const char* why = csr_check(c->m, c->n, indptr, indices, nnz)) return fail(c, PMF_EINVAL, std::string("pmf_set_v_csr_f32: ") + why);
   HIPCHK(c, hipSetDevice(c->device));
   PMFCHK(dgrow(c, &c->dIndptr, (size_t)c->mp + 1));
   PMFCHK(dgrow(c, &c->dIndices, (size_t)nnz));
@@ -318,6 +320,12 @@ int pmf_set_v_csr_f32(pmf_ctx* c, const int64_t* indptr, const int32_t* indices,
     c->csr_dense = true;
     PMFCHK(local_vnorm(c));
   }
+  return PMF_OK;
+}
+
+int pmf_check_csr(int64_t m, int64_t n, const int64_t* indptr, const int32_t* indices, int64_t nnz) {
+  if (m < 1 || n < 1 || !indptr || (nnz > 0 && !indices) || nnz < 0) return fail(nullptr, PMF_EINVAL, "pmf_check_csr: bad arguments");
+  if (const char* why = csr_check(m, n, indptr, indices, nnz)) return fail(nullptr, PMF_EINVAL, std::string("pmf_check_csr: ") + why);
   return PMF_OK;
 }
 

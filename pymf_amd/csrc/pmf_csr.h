@@ -475,7 +475,10 @@ __global__ __launch_bounds__(256, 1) void k_snmf_csr_fused(const int64_t* __rest
     if (wv == 1) put(0);
     __syncthreads();
     if (wv == 0) add(0);
-  } else {                                        // tiny n*k: one region, three rounds
+  } else {                                        // tiny n*k: one region, three rounds.  2 NS KiB > 4 np KP B means NT = 4 at
+                                                  // np = 64 or NT = 8 at np = 128 (both k_snmf_csr_mfma's) or NT = 8 at np = 64:
+                                                  // more bases than columns, H H^T singular -- kept for that call alone, see
+                                                  // snmf_csr_fused_iteration
     for (int src = 1; src < 4; ++src) {
       if (wv == src) put(0);
       __syncthreads();

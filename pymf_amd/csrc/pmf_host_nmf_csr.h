@@ -19,20 +19,27 @@ void nmf_csr_left(pmf_ctx* c) {
   choose_stat_site(c, false);
 }
 
+// The CSR image of an m x n matrix as pmf_set_v_csr_f32 takes it, checked on the host before anything is uploaded: the kernels
+// use a column index as an LDS index and the differences of indptr as trip counts.  Entries of a row may come in any order and
+// repeat (they add up).  nullptr: well-formed; else what is wrong.
+const char* csr_check(int64_t m, int64_t n, const int64_t* indptr, const int32_t* indices, int64_t nnz) {
+  if (indptr[0] != 0 || indptr[m] != nnz) return "indptr[0] must be 0 and indptr[m] must be nnz";
+  for (int64_t r = 0; r < m; ++r)
+    if (indptr[r + 1] < indptr[r]) return "indptr must not decrease";
+  for (int64_t e = 0; e < nnz; ++e)
+    if (indices[e] < 0 || indices[e] >= n) return "column index out of range";
+  return nullptr;
+}
+
 // pmf_set_v_csr_f32 on an NMF context.  The H step needs the rows of V^T: a stable counting sort of the entries by column, on the
 // host from the caller's arrays (rows ascending within a column, entries of one (row, column) pair in stored order -- a fixed
 // summation order), uploaded next to the CSR arrays.
 int nmf_csr_set_v(pmf_ctx* c, const int64_t* indptr, const int32_t* indices, const float* vals, int64_t nnz) {
   if (c->nb > 1) return fail(c, PMF_EINVAL, "NMF on CSR data: num_bases > 128 is not supported by this build");
   if (c->nranks > 1 || multi_rank(c)) return fail(c, PMF_EINVAL, "NMF on CSR data: one rank only in this build (nranks > 1)");
-  if (indptr[0] != 0 || indptr[c->m] != nnz) return fail(c, PMF_EINVAL, "pmf_set_v_csr_f32: indptr[0] must be 0 and indptr[m] must be nnz");
-  for (int64_t r = 0; r < c->m; ++r)
-    if (indptr[r + 1] < indptr[r]) return fail(c, PMF_EINVAL, "pmf_set_v_csr_f32: indptr must not decrease");
+  if (const char* why = csr_check(c->m, c->n, indptr, indices, nnz)) return fail(c, PMF_EINVAL, std::string("pmf_set_v_csr_f32: ") + why);
   std::vector<int64_t> tip((size_t)c->np + 1, 0);
-  for (int64_t e = 0; e < nnz; ++e) {
-    if (indices[e] < 0 || indices[e] >= c->n) return fail(c, PMF_EINVAL, "pmf_set_v_csr_f32: column index out of range");
-    ++tip[(size_t)indices[e] + 1];
-  }
+  for (int64_t e = 0; e < nnz; ++e) ++tip[(size_t)indices[e] + 1];
   for (int64_t q = 0; q < c->np; ++q) tip[(size_t)q + 1] += tip[(size_t)q];   // (columns >= n: empty rows of V^T)
   std::vector<int32_t> tind((size_t)nnz);
   std::vector<float> tval((size_t)nnz);

@@ -103,7 +103,7 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     }
   } else if (c->algo == PMF_ALGO_SNMF && use_csr(c)) {
     st.site = SITE_CSR_PASS;
-    st.name = "k_snmf_csr_mfma (one pass per iteration)";
+    st.name = "k_snmf_csr_pass";                  // until the first launch: launch_csr_mfma / launch_csr_fused name their instantiation
     st.flops = 4.0 * nnz * k + 4.0 * m * k * k;                  // SURVEY: SpMM, (.) inv, W^T V, W^T W
     st.exec_flops = 4.0 * nnz * k + m * k * (k + 16.0);          // V M, W^T V, upper triangle of W^T W
     st.bytes = 4.0 * m * k + 8.0 * nnz + 8.0 * (m + 1.0);

@@ -362,9 +362,16 @@ int materialize_w(pmf_ctx* c) {
   return rc;
 }
 
+// pmf_kernel_stats names the instantiation that runs: the launch itself writes it (choose_stat_site cannot know the dispatch)
+void name_csr_pass(pmf_ctx* c, const char* kernel) {
+  if (c->stat.site == SITE_CSR_PASS && c->stat.name != kernel) c->stat.name = kernel;
+}
+
 // CSR SNMF: update_w and the (P | S) partials of update_h in one pass over the CSR rows.
 template <int NT>
 int launch_csr_fused(pmf_ctx* c, int wgs) {
+  static const std::string kname = "k_snmf_csr_fused<" + std::to_string(NT) + ">";
+  name_csr_pass(c, kname.c_str());
   const size_t smem = ((size_t)2 * c->np * c->KP + 4 * 16 * c->KP) * sizeof(float);
   static bool attr_done_dev[PMF_MAX_DEVICES] = {};   // the attribute is per device
   bool& attr_done = attr_done_dev[pmf_current_device()];
@@ -382,6 +389,8 @@ int launch_csr_fused(pmf_ctx* c, int wgs) {
 
 template <int NT, int NTP>
 int launch_csr_mfma(pmf_ctx* c, int wgs) {
+  static const std::string kname = "k_snmf_csr_mfma<" + std::to_string(NT) + "," + std::to_string(NTP) + ">";
+  name_csr_pass(c, kname.c_str());
   const size_t smem = ((size_t)16 * NTP * 16 * NT + 64 * 16 * NTP) * sizeof(float) + 16;
   static bool attr_done_dev[PMF_MAX_DEVICES] = {};   // the attribute is per device
   bool& attr_done = attr_done_dev[pmf_current_device()];
@@ -439,6 +448,10 @@ int snmf_csr_fused_iteration(pmf_ctx* c) {
     case 1: PMFCHK(launch_csr_fused<1>(c, wgs)); break;
     case 2: PMFCHK(launch_csr_fused<2>(c, wgs)); break;
     case 4: PMFCHK(launch_csr_fused<4>(c, wgs)); break;
+    // NT = 8 arrives here with np = 64 only (np = 128 is k_snmf_csr_mfma<8,8>, np >= 192 fails csr_fused_ok: 2 np KP floats
+    // beyond 160 KiB): more than 64 bases on at most 64 columns, so H H^T has rank <= n < num_bases and the step has no
+    // meaning (snmf.py:69 inverts a singular matrix).  The instantiation stays so that such a call behaves as on every other
+    // shape and does not end in "bad NT"; no solvable problem runs it (tests/snmf_csr_cases.py: dead_forms).
     case 8: PMFCHK(launch_csr_fused<8>(c, wgs)); break;
     default: return fail(c, PMF_EINVAL, "bad NT");
   }
