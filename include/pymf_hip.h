@@ -43,6 +43,7 @@
  *   pmf_svd_decompose / pmf_svd_get  SVD.factorize, U / S / V  pymf/svd.py:110-158 (algo 12; PCA: pymf/pca.py)
  *   pmf_cur_sqnorms       CUR.sample_probability       pymf/cur.py:84-97 (algo 14)
  *   pmf_cur_compute / pmf_cur_get  CUR.computeUCR, C / U / R  pymf/cur.py:99-120 (CMD: pymf/cmd.py)
+ *   pmf_cur_ferr          CUR.frobenius_norm on sparse data  pymf/svd.py:92-107
  *   pmf_cur_leverage      CURSL.sample_probability     pymf/cursl.py:65-91 (algo 14)
  *   pmf_greedy_select     self.select of GREEDY        pymf/greedy.py:105-158 (algo 15; GREEDYCUR.sample: pymf/greedycur.py:62-68)
  *
@@ -110,8 +111,8 @@ const char* pmf_last_error(const pmf_ctx* ctx);   /* ctx may be NULL: last creat
 int pmf_set_v_dense_f32(pmf_ctx* ctx, const float* V, int64_t ld);
 /* V as CSR (m_local rows): indptr[m_local+1] int64, indices[nnz] int32, vals[nnz] f32.  Copied.  Semantics: the dense
  * algorithm on the matrix these arrays describe (entries of one (row, column) pair add up); pmf_frobenius and
- * PMF_COMPUTE_ERR refuse CSR data.  SNMF and NMF contexts only; every other family returns PMF_EINVAL.
- * Both check the arrays on the host before anything is uploaded (indptr from 0 to nnz and not decreasing, indices in
+ * PMF_COMPUTE_ERR refuse CSR data.  SNMF, NMF and CUR / CMD contexts only; every other family returns PMF_EINVAL.
+ * All check the arrays on the host before anything is uploaded (indptr from 0 to nnz and not decreasing, indices in
  * [0, n); the entries of a row may come in any order and repeat): malformed input is PMF_EINVAL and leaves the resident data
  * as it was.  pmf_check_csr: the same check of the arrays alone, for an m x n matrix, without a context or a device (the
  * message through pmf_last_error(NULL)).
@@ -119,7 +120,13 @@ int pmf_set_v_dense_f32(pmf_ctx* ctx, const float* V, int64_t ld);
  *   NMF:  never a dense V.  The call builds the CSR arrays of V^T on the host by a stable counting sort and uploads them beside the rows; both half
  *         steps then run one gather-form kernel on stored entries (pmf_path_name: "nmf_csr_gather<NT>"), with the
  *         same bits on every run.  PMF_EINVAL, the message naming the limit, for num_bases > 128 and for more than
- *         one rank (nranks > 1, or a host / IPC transport installed).  pmf_stream_* refuses while CSR data is resident. */
+ *         one rank (nranks > 1, or a host / IPC transport installed).  pmf_stream_* refuses while CSR data is resident.
+ *   CUR / CMD (algo 14): never a dense V.  Beyond the check above the column indices must ascend strictly within a row (a
+ *         repeated entry would make the norms (a + b)^2 instead of a^2 + b^2): PMF_EINVAL otherwise.  The call builds the CSR
+ *         arrays of V^T as for NMF, uploads both images and releases a resident dense V; a later dense upload releases the
+ *         sparse arrays.  pmf_path_name: "cur_csr".  One rank only.  pmf_cur_sqnorms, pmf_cur_compute, pmf_cur_get and
+ *         pmf_cur_ferr work on the stored entries; pmf_cur_leverage, pmf_frobenius, pmf_factorize (PMF_COMPUTE_ERR included),
+ *         pmf_greedy_select, pmf_sivm_select and pmf_stream_* return PMF_EINVAL while CSR data is resident, and say so. */
 int pmf_set_v_csr_f32(pmf_ctx* ctx, const int64_t* indptr, const int32_t* indices,
                       const float* vals, int64_t nnz);
 int pmf_check_csr(int64_t m, int64_t n, const int64_t* indptr, const int32_t* indices, int64_t nnz);
@@ -395,10 +402,18 @@ int pmf_svd_get(pmf_ctx* ctx, double* U, double* S, double* V);
  * ccnt NULL means all ones; indices need not be sorted or distinct.  PMF_EINVAL for an index out of range or a count < 1.  It
  * leaves W = C U and H = R (float32), so that pmf_frobenius is svd.py's ||data - C U R||.
  * pmf_cur_get: C (m x nc), U (nc x nr) and R (nr x n) of the last pmf_cur_compute as float64, row-major, C and R scaled as
- * the reference returns them; a NULL pointer skips that factor.  PMF_EINVAL when the resident V has not been decomposed. */
+ * the reference returns them; a NULL pointer skips that factor.  PMF_EINVAL when the resident V has not been decomposed.
+ * On CSR data (pmf_set_v_csr_f32) the three calls above read stored entries only: the norms by k_cur_csr_sqnorms, the gathers by
+ * k_cur_csr_gather, the middle product by k_cur_csr_mid (walks the selected rows and their crossing columns, float64, chunk
+ * partials added in a fixed order); Gram matrices, pseudo-inverses and the host finish are those of dense data.  C and R come
+ * back dense.  Two runs give the same bits.
+ * pmf_cur_ferr: CSR data only: *out = ||data - C U R||_F of the last pmf_cur_compute in float64, from the identity
+ * ||data||^2 - 2 <U, C^T data R^T> + <(C^T C) U, U (R R^T)> (clamped at 0 before the root) on quantities that call formed:
+ * no dense image.  PMF_EINVAL on dense data (pmf_frobenius is the error there) and before a pmf_cur_compute. */
 int pmf_cur_sqnorms(pmf_ctx* ctx, double* row_sq, double* col_sq);
 int pmf_cur_compute(pmf_ctx* ctx, const int32_t* rid, const int32_t* rcnt, int32_t nr, const int32_t* cid, const int32_t* ccnt, int32_t nc);
 int pmf_cur_get(pmf_ctx* ctx, double* C, double* U, double* R);
+int pmf_cur_ferr(pmf_ctx* ctx, double* out);
 
 /* CURSL (pymf/cursl.py: CMD with statistical leverage scores as sampling probabilities) on a CUR / CMD context (algo 14).
  * pmf_cur_leverage: row_lev [m] = the squared row norms of the leading min(k_rows, rank) left singular vectors of the resident

@@ -87,6 +87,7 @@ SYMBOLS = [
     ("pmf_cur_sqnorms", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p]),
     ("pmf_cur_compute", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_int32]),
     ("pmf_cur_get", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    ("pmf_cur_ferr", _c.c_int, [_ctx, _c.POINTER(_c.c_double)]),
     ("pmf_cur_leverage", _c.c_int, [_ctx, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_void_p]),
     ("pmf_stream_begin", _c.c_int, [_ctx, _c.c_uint32, _c.c_int64]),
     ("pmf_stream_tile", _c.c_int, [_ctx, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int64]),
@@ -554,6 +555,12 @@ class Context(object):
         R = np.zeros((nr, self.n), dtype=np.float64) if "R" in want else None
         self._chk(self._lib.pmf_cur_get(self._h, *(None if a is None else a.ctypes.data for a in (C, U, R))))
         return C, U, R
+
+    def cur_ferr(self):
+        """CUR / CMD on CSR data: ||data - C U R||_F of the last cur_compute from the trace identity, float64 (pmf_cur_ferr)."""
+        out = ctypes.c_double(0.0)
+        self._chk(self._lib.pmf_cur_ferr(self._h, ctypes.byref(out)))
+        return float(out.value)
 
     def get_h64(self):
         H = np.empty((self.k, self.n), dtype=np.float64)

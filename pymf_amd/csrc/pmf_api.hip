@@ -46,6 +46,7 @@
 #include "pmf_aa.h"
 #include "pmf_svd.h"
 #include "pmf_cur.h"
+#include "pmf_cur_csr.h"
 #include "pmf_lev.h"
 #include "pmf_greedy.h"
 
@@ -70,6 +71,7 @@
 #include "pmf_host_gsat.h"
 #include "pmf_host_aa.h"
 #include "pmf_host_svd.h"
+#include "pmf_host_cur_csr.h"
 #include "pmf_host_cur.h"
 #include "pmf_host_greedy.h"
 #include "pmf_host_factorize.h"
@@ -274,6 +276,7 @@ static int set_v_dense(pmf_ctx* c, const void* V, bool f64, int64_t ld, const ch
   if (!c || !V || ld < c->n) return fail(c, PMF_EINVAL, std::string(who) + ": bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
   PMFCHK(sivm_csc_left(c));
+  PMFCHK(cur_csr_left(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
   PMFCHK(f64 ? upload_rows(c, c->dV, c->np, static_cast<const double*>(V), ld, c->m, c->n)
@@ -292,7 +295,8 @@ int pmf_set_v_csr_f32(pmf_ctx* c, const int64_t* indptr, const int32_t* indices,
   if (!c || !indptr || (nnz > 0 && (!indices || !vals)) || nnz < 0)
     return fail(c, PMF_EINVAL, "pmf_set_v_csr_f32: bad arguments");
   if (c->algo == PMF_ALGO_NMF) return nmf_csr_set_v(c, indptr, indices, vals, nnz);
-  if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF and NMF");
+  if (c->algo == PMF_ALGO_CUR) return cur_csr_set_v(c, indptr, indices, vals, nnz);
+  if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF, NMF and CUR / CMD");
   // refused arrays never reach the device: what is resident stays as it was
   if (const char* why = csr_check(c->m, c->n, indptr, indices, nnz)) return fail(c, PMF_EINVAL, std::string("pmf_set_v_csr_f32: ") + why);
   HIPCHK(c, hipSetDevice(c->device));
@@ -353,6 +357,7 @@ static int fill(pmf_ctx* c, float* X, int64_t ld, int64_t rows, int64_t cols, in
 int pmf_fill_v_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   if (!c) return PMF_EINVAL;
   PMFCHK(sivm_csc_left(c));
+  PMFCHK(cur_csr_left(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
   PMFCHK(fill(c, c->dV, c->np, c->m, c->n, row0, seed));
@@ -484,6 +489,7 @@ static int run_step(pmf_ctx* c, bool w_step) {
 int pmf_update_w(pmf_ctx* c) { return run_step(c, true); }
 int pmf_update_h(pmf_ctx* c) { return run_step(c, false); }
 int pmf_frobenius(pmf_ctx* c, double* out) {
+  PMFCHK(cur_csr_refuse(c, "pmf_frobenius"));
   PMFCHK(need(c, true, true, true));
   if (!out) return fail(c, PMF_EINVAL, "out is NULL");
   return algo_row(c).frobenius(c, out);
@@ -493,6 +499,7 @@ int pmf_factorize(pmf_ctx* c, int32_t niter, uint32_t flags, double conv_eps, do
                   int32_t* iters_done, int32_t* converged_at) {
   const bool cw = flags & PMF_COMPUTE_W, ch = flags & PMF_COMPUTE_H, ce = flags & PMF_COMPUTE_ERR;
   if (!c) return PMF_EINVAL;
+  PMFCHK(cur_csr_refuse(c, ce ? "pmf_factorize with PMF_COMPUTE_ERR" : "pmf_factorize"));
   const AlgoRow& a = algo_row(c);
   if (a.instead) return refuse_step(c, "iteration");
   const Operands r = a.loop_reads(cw, ch);
@@ -592,6 +599,7 @@ int pmf_gsat_get_d(pmf_ctx* c, double* D) {
 int pmf_greedy_select(pmf_ctx* c, int32_t transposed, int32_t nsel, int32_t* select) {
   if (!c || !select) return fail(c, PMF_EINVAL, "pmf_greedy_select: bad arguments");
   if (c->algo != PMF_ALGO_GREEDY && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_greedy_select: GREEDY and CUR / CMD contexts only");
+  PMFCHK(cur_csr_refuse(c, "pmf_greedy_select"));
   PMFCHK(need(c, true, false, false));
   return greedy_select_host(c, transposed != 0, nsel, select);
 }
@@ -599,6 +607,7 @@ int pmf_greedy_select(pmf_ctx* c, int32_t transposed, int32_t nsel, int32_t* sel
 int pmf_sivm_select(pmf_ctx* c, int32_t transposed, int32_t nsel, int32_t metric, int32_t init, int32_t path, int32_t* select) {
   if (!c || !select) return fail(c, PMF_EINVAL, "pmf_sivm_select: bad arguments");
   if (c->algo != PMF_ALGO_SIVM && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_sivm_select: SIVM and CUR / CMD contexts only");
+  PMFCHK(cur_csr_refuse(c, "pmf_sivm_select"));
   PMFCHK(need(c, true, false, false));
   return sivm_select_host(c, transposed != 0, nsel, metric, init, path, select);
 }
@@ -665,6 +674,13 @@ int pmf_cur_get(pmf_ctx* c, double* C, double* U, double* R) {
   if (c && c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_cur_get: CUR / CMD contexts only");
   PMFCHK(need(c, true, false, false));
   return cur_get(c, C, U, R);
+}
+
+int pmf_cur_ferr(pmf_ctx* c, double* out) {
+  if (!c || !out) return fail(c, PMF_EINVAL, "pmf_cur_ferr: bad arguments");
+  if (c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "pmf_cur_ferr: CUR / CMD contexts only");
+  PMFCHK(need(c, true, false, false));
+  return cur_ferr(c, out);
 }
 
 int pmf_cluster_set_assigned(pmf_ctx* c, const int32_t* assigned) {
@@ -740,6 +756,7 @@ int pmf_rnmf_set_s_f32(pmf_ctx* c, const float* S) {
 int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (c) c->hd_synced = false;
   if (!c) return PMF_EINVAL;
+  PMFCHK(cur_csr_refuse(c, "pmf_stream_*"));
   if (!algo_row(c).streamable)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (nmf_csr(c)) return fail(c, PMF_EINVAL, "pmf_stream_*: not on an NMF context that holds CSR data (set dense data, or none, first)");

@@ -223,6 +223,13 @@ struct pmf_ctx {
   std::vector<double> cur_dc, cur_dr, cur_U;
   bool cur_valid = false;       // they belong to the current V.  <- V
   int opt_profile_cur = 0;      // pmf_set_option("profile_cur"): pmf_profile_enable times 0 the cross product, 1 k_lev_f64, 2 k_cur_sqnorms
+  // CUR / CMD on CSR data (pmf_cur_csr.h, pmf_host_cur_csr.h): v_csr with both CSR images resident (dIndptr ..., dTIndptr ...) and no
+  // dV; on the host the row pointers (the chunk count of k_cur_csr_mid follows the longest selected row), ||data||^2 as the sum
+  // of the row norms in row order, and the error of the last pmf_cur_compute by the trace identity (pmf_cur_ferr)
+  std::vector<int64_t> cur_ip;
+  double cur_vnorm2 = 0.0, cur_ferr = 0.0;
+  bool cur_vnorm2_valid = false;   // <- V
+  bool cur_ferr_valid = false;     // <- V (with cur_valid)
   // GREEDY / GREEDYCUR (pmf_greedy.h): the float64 Gram matrix on the short side of V and the rows of its eigenvectors ([qp][qp]
   // each), on the host the eigenvalues and the indices of those above svd.py's 1e-8 cut in descending order; pinv(W)^T [mp][KP]
   // float32, the operand of H = pinv(W) data.  The selection itself is read through dSvSel / sv_have_select (SIVM's).
@@ -433,7 +440,7 @@ void v_replaced(pmf_ctx* c) {
   c->vnorm_valid = c->vnorm_local_valid = c->ps_valid = c->num_valid = c->trace_ready = c->c_valid = false;
   c->cl_sums_valid = c->cl_err_valid = c->cl_mu_valid = false;
   c->svd_valid = false;
-  c->cur_valid = false;
+  c->cur_valid = c->cur_ferr_valid = c->cur_vnorm2_valid = false;
   c->gr_eig_valid = false;
 }
 void w_replaced(pmf_ctx* c, bool by_caller) {   // by_caller: uploaded or filled through the ABI (not the NNDSVD init, not a restored snapshot)

@@ -4,8 +4,11 @@
 
 namespace {
 
-int cur_check(pmf_ctx* c, const char* who) {
-  if (c->v_csr || !c->dV) return fail(c, PMF_EINVAL, std::string(who) + ": dense resident data only");
+// csr_ok: the entry point has a form on CSR data (pmf_host_cur_csr.h)
+int cur_check(pmf_ctx* c, const char* who, bool csr_ok = false) {
+  if (csr_ok && cur_csr(c)) { if (!c->dIndptr) return fail(c, PMF_EINVAL, std::string(who) + ": no resident data"); }
+  else if (c->v_csr) return cur_csr_refuse(c, who);
+  else if (!c->dV) return fail(c, PMF_EINVAL, std::string(who) + ": dense resident data only");
   if (multi_rank(c)) return fail(c, PMF_EINVAL, std::string(who) + ": one rank only in this build");
   return PMF_OK;
 }
@@ -32,7 +35,8 @@ int sqnorms_f64(pmf_ctx* c, DevTemps& tmp, bool timed, double** sq) {
 
 // cur.py:84-97 without the normalisation: the row sums (m) and column sums (n) of data^2
 int cur_sqnorms(pmf_ctx* c, double* row_sq, double* col_sq) {
-  PMFCHK(cur_check(c, "pmf_cur_sqnorms"));
+  PMFCHK(cur_check(c, "pmf_cur_sqnorms", true));
+  if (cur_csr(c)) return cur_csr_sqnorms(c, row_sq, col_sq);
   DevTemps tmp;
   double* out = nullptr;
   PMFCHK(sqnorms_f64(c, tmp, true, &out));
@@ -184,9 +188,10 @@ int cur_indices(pmf_ctx* c, const int32_t* id, const int32_t* cnt, int n, int64_
 // U = pinv(C) data pinv(R) = (C^T C)^+ (dc o (Cg^T data Rg^T) o dr) (R R^T)^+ (pmf_cur.h).  The data are read once by k_prod_f64:
 // rows <= cols: T [mp][rp] = V Rg^T, then M = Cg^T T; otherwise T' [cp][np] = Cg^T V, then M = T' Rg^T (float64 MFMA, dgemm64).
 // The c x r sized rest runs on the host in float64 in a fixed order.  Leaves W = C U and H = R, so that pmf_frobenius is
-// ||data - C U R|| (svd.py:92-107).
+// ||data - C U R|| (svd.py:92-107).  On CSR data the gathers and M come from the stored entries (cur_csr_mid) and the error from
+// the trace identity (cur_csr_ferr, read by pmf_cur_ferr); everything between is shared.
 int cur_compute(pmf_ctx* c, const int32_t* rid, const int32_t* rcnt, int nr, const int32_t* cid, const int32_t* ccnt, int nc) {
-  PMFCHK(cur_check(c, "pmf_cur_compute"));
+  PMFCHK(cur_check(c, "pmf_cur_compute", true));
   if (!rid || !cid) return fail(c, PMF_EINVAL, "pmf_cur_compute: rid and cid must not be NULL");
   const int lim = std::min(c->k, PMF_CUR_MAX_RANK);
   if (nr < 1 || nc < 1 || nr > lim || nc > lim)
@@ -195,13 +200,15 @@ int cur_compute(pmf_ctx* c, const int32_t* rid, const int32_t* rcnt, int nr, con
   std::vector<double> dr, dc;
   PMFCHK(cur_indices(c, rid, rcnt, nr, c->m, hr, dr));
   PMFCHK(cur_indices(c, cid, ccnt, nc, c->n, hc, dc));
-  c->cur_valid = false;
+  c->cur_valid = c->cur_ferr_valid = false;
   PMFCHK(cur_alloc(c));
   const int64_t mp = c->mp;
   const int np = c->np, cp = (int)round_up(nc, 64), rp = (int)round_up(nr, 64), KP = c->KP;
   const bool trans = c->m > c->n;
   std::vector<double> M((size_t)cp * rp);
-  {
+  if (cur_csr(c)) {
+    PMFCHK(cur_csr_mid(c, hr, hc, cp, rp, M));
+  } else {
     DevTemps tmp;
     int *dcid = nullptr, *drid = nullptr;
     double *side = nullptr, *T = nullptr, *dM = nullptr;
@@ -258,6 +265,7 @@ int cur_compute(pmf_ctx* c, const int32_t* rid, const int32_t* rcnt, int nr, con
     h_replaced(c, false, true);
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  if (cur_csr(c)) PMFCHK(cur_csr_ferr(c, M, rp, dc, dr, U));
   c->cur_nr = nr; c->cur_nc = nc;
   c->cur_dr = dr; c->cur_dc = dc; c->cur_U = U;
   c->cur_valid = true;

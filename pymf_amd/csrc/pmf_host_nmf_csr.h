@@ -31,38 +31,27 @@ const char* csr_check(int64_t m, int64_t n, const int64_t* indptr, const int32_t
   return nullptr;
 }
 
-// pmf_set_v_csr_f32 on an NMF context.  The H step needs the rows of V^T: a stable counting sort of the entries by column, on the
-// host from the caller's arrays (rows ascending within a column, entries of one (row, column) pair in stored order -- a fixed
-// summation order), uploaded next to the CSR arrays.
+// The CSR arrays of V^T from those of V (checked by csr_check): a stable counting sort of the entries by column, on the host --
+// rows ascending within a column, entries of one (row, column) pair in stored order (a fixed summation order).  tip [np + 1]
+// (columns >= n: empty rows of V^T), tind and tval [nnz]; ip [mp + 1] = indptr with the pad rows empty.
+struct CsrPair {
+  std::vector<int64_t> ip, tip;
+  std::vector<int32_t> tind;
+  std::vector<float> tval;
+};
+void csr_transpose_host(const pmf_ctx* c, const int64_t* indptr, const int32_t* indices, const float* vals, int64_t nnz, CsrPair& p);
+int csr_upload_pair(pmf_ctx* c, const CsrPair& p, const int32_t* indices, const float* vals, int64_t nnz);   // (both below nmf_csr_set_v)
+
+// pmf_set_v_csr_f32 on an NMF context.  The H step needs the rows of V^T: csr_transpose_host, uploaded next to the CSR arrays.
 int nmf_csr_set_v(pmf_ctx* c, const int64_t* indptr, const int32_t* indices, const float* vals, int64_t nnz) {
   if (c->nb > 1) return fail(c, PMF_EINVAL, "NMF on CSR data: num_bases > 128 is not supported by this build");
   if (c->nranks > 1 || multi_rank(c)) return fail(c, PMF_EINVAL, "NMF on CSR data: one rank only in this build (nranks > 1)");
   if (const char* why = csr_check(c->m, c->n, indptr, indices, nnz)) return fail(c, PMF_EINVAL, std::string("pmf_set_v_csr_f32: ") + why);
-  std::vector<int64_t> tip((size_t)c->np + 1, 0);
-  for (int64_t e = 0; e < nnz; ++e) ++tip[(size_t)indices[e] + 1];
-  for (int64_t q = 0; q < c->np; ++q) tip[(size_t)q + 1] += tip[(size_t)q];   // (columns >= n: empty rows of V^T)
-  std::vector<int32_t> tind((size_t)nnz);
-  std::vector<float> tval((size_t)nnz);
-  {
-    std::vector<int64_t> at(tip.begin(), tip.end() - 1);
-    for (int64_t r = 0; r < c->m; ++r)
-      for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
-        const int64_t d = at[(size_t)indices[e]]++;
-        tind[(size_t)d] = (int32_t)r;
-        tval[(size_t)d] = vals[e];
-      }
-  }
-  std::vector<int64_t> ip((size_t)c->mp + 1);
-  for (int64_t r = 0; r <= c->mp; ++r) ip[(size_t)r] = indptr[std::min(r, c->m)];
+  CsrPair p;
+  csr_transpose_host(c, indptr, indices, vals, nnz, p);
 
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  PMFCHK(dgrow(c, &c->dIndptr, (size_t)c->mp + 1));
-  PMFCHK(dgrow(c, &c->dIndices, (size_t)nnz));
-  PMFCHK(dgrow(c, &c->dVals, (size_t)nnz));
-  PMFCHK(dgrow(c, &c->dTIndptr, (size_t)c->np + 1));
-  PMFCHK(dgrow(c, &c->dTIndices, (size_t)nnz));
-  PMFCHK(dgrow(c, &c->dTVals, (size_t)nnz));
   if (!c->dHT) {
     int dev = 0, cus = 256;
     hipDeviceProp_t prop;
@@ -75,15 +64,7 @@ int nmf_csr_set_v(pmf_ctx* c, const int64_t* indptr, const int32_t* indices, con
     PMFCHK(dalloc(c, &c->dSw, (size_t)c->KP * c->KP));
     PMFCHK(dalloc(c, &c->dSpSlab, (size_t)c->sp_wgs_cap * c->KP * c->KP));
   }
-  HIPCHK(c, hipMemcpyAsync(c->dIndptr, ip.data(), ip.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->dTIndptr, tip.data(), tip.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-  if (nnz) {
-    HIPCHK(c, hipMemcpyAsync(c->dIndices, indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dVals, vals, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dTIndices, tind.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dTVals, tval.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));       // (the host arrays above leave scope)
+  PMFCHK(csr_upload_pair(c, p, indices, vals, nnz));
   c->nnz = nnz; c->have_v = true; c->v_csr = true; c->csr_dense = false;
   v_replaced(c);
   // the dense paths that may have run since the last CSR upload keep dH and g_valid, not H^T and W^T W
@@ -91,6 +72,45 @@ int nmf_csr_set_v(pmf_ctx* c, const int64_t* indptr, const int32_t* indices, con
   if (c->path_dense.empty()) c->path_dense = c->path;
   c->path = "nmf_csr_gather<" + std::to_string(c->NT) + ">";
   choose_stat_site(c, false);
+  return PMF_OK;
+}
+
+void csr_transpose_host(const pmf_ctx* c, const int64_t* indptr, const int32_t* indices, const float* vals, int64_t nnz, CsrPair& p) {
+  p.tip.assign((size_t)c->np + 1, 0);
+  for (int64_t e = 0; e < nnz; ++e) ++p.tip[(size_t)indices[e] + 1];
+  for (int64_t q = 0; q < c->np; ++q) p.tip[(size_t)q + 1] += p.tip[(size_t)q];
+  p.tind.resize((size_t)nnz);
+  p.tval.resize((size_t)nnz);
+  {
+    std::vector<int64_t> at(p.tip.begin(), p.tip.end() - 1);
+    for (int64_t r = 0; r < c->m; ++r)
+      for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+        const int64_t d = at[(size_t)indices[e]]++;
+        p.tind[(size_t)d] = (int32_t)r;
+        p.tval[(size_t)d] = vals[e];
+      }
+  }
+  p.ip.resize((size_t)c->mp + 1);
+  for (int64_t r = 0; r <= c->mp; ++r) p.ip[(size_t)r] = indptr[std::min(r, c->m)];
+}
+
+// both images onto the device (dIndptr ..., dTIndptr ...), the buffers sized anew; returns with the copies done
+int csr_upload_pair(pmf_ctx* c, const CsrPair& p, const int32_t* indices, const float* vals, int64_t nnz) {
+  PMFCHK(dgrow(c, &c->dIndptr, (size_t)c->mp + 1));
+  PMFCHK(dgrow(c, &c->dIndices, (size_t)nnz));
+  PMFCHK(dgrow(c, &c->dVals, (size_t)nnz));
+  PMFCHK(dgrow(c, &c->dTIndptr, (size_t)c->np + 1));
+  PMFCHK(dgrow(c, &c->dTIndices, (size_t)nnz));
+  PMFCHK(dgrow(c, &c->dTVals, (size_t)nnz));
+  HIPCHK(c, hipMemcpyAsync(c->dIndptr, p.ip.data(), p.ip.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->dTIndptr, p.tip.data(), p.tip.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  if (nnz) {
+    HIPCHK(c, hipMemcpyAsync(c->dIndices, indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dVals, vals, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dTIndices, p.tind.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dTVals, p.tval.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));       // (the host arrays may leave scope)
   return PMF_OK;
 }
 

@@ -19,6 +19,16 @@ included): set them by hand, or let a subclass such as CMD set them.
 
 Supported: dense data, one rank, at most 128 sampled rows and 128 sampled columns.  scipy.sparse data raises TypeError, a
 multi-rank world NotImplementedError, more rows or columns ValueError.
+
+scipy.sparse data (opt-in: `mdl.accept_sparse = True`, the switch NMF has; CUR and CMD only).  The matrix is converted once
+to canonical CSR (tocsr(), duplicates summed, indices sorted, float32 values) and stays sparse on the device: the norms, the
+gathers and the middle product read stored entries only (k_cur_csr_sqnorms, k_cur_csr_gather, k_cur_csr_mid),
+the rest is the dense path.  factorize(), sample_probability() and computeUCR() give what the dense run on toarray() gives,
+with the same draws.  Deliberate deviations from the reference's sparse branch: U, S, V come back as dense float64 arrays (the
+reference returns sparse C and R), and pinv is not routed through ARPACK with k = min(dim) - 1, which silently drops the
+smallest singular pair -- the yardstick is the dense path.  frobenius_norm() is evaluated in float64 without a dense image,
+ferr^2 = ||data||^2 - 2 <U, C^T data R^T> + <(C^T C) U, U (R R^T)> (clamped at 0), from what computeUCR() formed; it needs
+the factors of that call: a rebound U, S or V raises NotImplementedError.
 """
 import warnings
 
@@ -43,15 +53,22 @@ class CUR(SVD):
     >>> cur_mdl.factorize()
     """
 
+    accept_sparse = False     # opt-in: scipy.sparse data stays sparse on the device (CUR and CMD)
+    _TAKES_SPARSE = True      # the subclasses without a sparse device path switch it off
+
     def __init__(self, data, k=-1, rrank=0, crank=0):          # cur.py:59-66
         SVD.__init__(self, data, k=k, rrank=rrank, crank=rrank)
         self._rset = range(self._rows)
         self._cset = range(self._cols)
         self._fresh = False         # the context holds the data of this factorize() call
 
+    def _sparse_run(self):
+        """`data` is a scipy.sparse matrix and this object takes it (accept_sparse; CUR and CMD)."""
+        return bool(self.accept_sparse) and self._TAKES_SPARSE and _is_sparse(self.data)
+
     def _check_supported(self):
-        if _is_sparse(self.data):
-            raise TypeError("CUR: scipy.sparse data is not supported (dense data only)")
+        if _is_sparse(self.data) and not self._sparse_run():
+            raise TypeError("CUR: scipy.sparse data is not supported (dense data only; CUR and CMD take it with accept_sparse = True)")
         if _dist.world().size > 1:
             raise NotImplementedError("CUR: one rank only (a multi-rank world is not supported)")
 
@@ -67,13 +84,24 @@ class CUR(SVD):
 
     def _upload(self):
         self._check_supported()
-        arr = np.asarray(self.data[:, :])
+        sparse = self._sparse_run()
+        if sparse:
+            arr = self.data.tocsr()
+            if not arr.has_canonical_format:
+                if arr is self.data:
+                    arr = arr.copy()                           # (the caller's matrix keeps its entries as they are)
+                arr.sum_duplicates()
+        else:
+            arr = np.asarray(self.data[:, :])
         if arr.dtype == np.float64 and not self.__dict__.get("_warned_f64", False):
             self._warned_f64 = True
             warnings.warn("CUR: float64 data is rounded to float32 on the device (norms, Gram matrices and the middle "
                           "product of the rounded data are formed in float64; DESIGN.md 3.15)", PrecisionWarning, stacklevel=3)
         ctx = self._context()
-        ctx.set_v_dense(arr)
+        if sparse:
+            ctx.set_v_csr(arr.indptr.astype(np.int64), arr.indices.astype(np.int32), arr.data.astype(np.float32))
+        else:
+            ctx.set_v_dense(arr)
         return ctx
 
     def sample(self, s, probs):                                # cur.py:69-82
@@ -131,6 +159,21 @@ class CUR(SVD):
         self.S = self._U
         self.V = self._R
         self._on_device = (self.U, self.S, self.V)
+
+    def frobenius_norm(self):                                  # svd.py:92-107
+        """||data - U S V||_F of the data that computeUCR() saw; on sparse data from the trace identity (module docstring)."""
+        if not self._sparse_run():
+            return SVD.frobenius_norm(self)
+        self._check_supported()
+        U, S, V = self.U, self.S, self.V                       # AttributeError before factorize(), as in the reference
+        cur = self._on_device
+        if self._ctx is None or cur is None:
+            raise AttributeError("CUR.frobenius_norm: computeUCR() has not run")
+        for name, have, want in zip("USV", (U, S, V), cur):
+            if have is not want:
+                raise NotImplementedError("CUR.frobenius_norm on scipy.sparse data: %s was rebound; the error comes from the "
+                                          "factors of the last computeUCR()" % name)
+        return self._ctx.cur_ferr()
 
     def _check_ranks(self):
         if self._rrank > MAX_RANK or self._crank > MAX_RANK:

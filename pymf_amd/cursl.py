@@ -30,6 +30,7 @@ class CURSL(CMD):
     >>> cur_mdl = CURSL(data, rrank=1, crank=2)
     >>> cur_mdl.factorize()
     """
+    _TAKES_SPARSE = False     # no sparse device path: accept_sparse changes nothing here
 
     def __init__(self, data, k=-1, rrank=0, crank=0):          # cursl.py:62-63
         CUR.__init__(self, data, k=k, rrank=rrank, crank=crank)

@@ -28,6 +28,7 @@ class GREEDYCUR(CUR):
     >>> cur_mdl = GREEDYCUR(data, rrank=1, crank=2)
     >>> cur_mdl.factorize()
     """
+    _TAKES_SPARSE = False     # no sparse device path: accept_sparse changes nothing here
 
     def _check_ranks(self):
         if self._rrank > MAX_BASES or self._crank > MAX_BASES:

@@ -34,6 +34,7 @@ class SIVM_CUR(CUR):
     >>> sivmcur_mdl = SIVM_CUR(data, rrank=1, crank=2)
     >>> sivmcur_mdl.factorize()
     """
+    _TAKES_SPARSE = False     # no sparse device path: accept_sparse changes nothing here
 
     def __init__(self, data, k=-1, rrank=0, crank=0, dist_measure='l2', init='origin'):   # sivm_cur.py:60-63
         CUR.__init__(self, data, k=k, rrank=rrank, crank=rrank)
