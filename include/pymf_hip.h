@@ -111,7 +111,8 @@ const char* pmf_last_error(const pmf_ctx* ctx);   /* ctx may be NULL: last creat
 int pmf_set_v_dense_f32(pmf_ctx* ctx, const float* V, int64_t ld);
 /* V as CSR (m_local rows): indptr[m_local+1] int64, indices[nnz] int32, vals[nnz] f32.  Copied.  Semantics: the dense
  * algorithm on the matrix these arrays describe (entries of one (row, column) pair add up); pmf_frobenius and
- * PMF_COMPUTE_ERR refuse CSR data.  SNMF, NMF and CUR / CMD contexts only; every other family returns PMF_EINVAL.
+ * PMF_COMPUTE_ERR refuse CSR data (PCA / SVD contexts excepted, below).  SNMF, NMF, CUR / CMD and PCA / SVD contexts only; every
+ * other family returns PMF_EINVAL.
  * All check the arrays on the host before anything is uploaded (indptr from 0 to nnz and not decreasing, indices in
  * [0, n); the entries of a row may come in any order and repeat): malformed input is PMF_EINVAL and leaves the resident data
  * as it was.  pmf_check_csr: the same check of the arrays alone, for an m x n matrix, without a context or a device (the
@@ -126,7 +127,15 @@ int pmf_set_v_dense_f32(pmf_ctx* ctx, const float* V, int64_t ld);
  *         arrays of V^T as for NMF, uploads both images and releases a resident dense V; a later dense upload releases the
  *         sparse arrays.  pmf_path_name: "cur_csr".  One rank only.  pmf_cur_sqnorms, pmf_cur_compute, pmf_cur_get and
  *         pmf_cur_ferr work on the stored entries; pmf_cur_leverage, pmf_frobenius, pmf_factorize (PMF_COMPUTE_ERR included),
- *         pmf_greedy_select, pmf_sivm_select and pmf_stream_* return PMF_EINVAL while CSR data is resident, and say so. */
+ *         pmf_greedy_select, pmf_sivm_select and pmf_stream_* return PMF_EINVAL while CSR data is resident, and say so.
+ *   PCA / SVD (algo 12): never a dense V.  The checks, the
+ *         transposed copy and the release of a resident dense V are CUR / CMD's, strictly ascending columns included; on top of
+ *         them min(rows, cols) padded to 64 must not exceed 1024 (the slab scheme of k_csr_gram).  pmf_path_name: "svd_csr".
+ *         One rank only.  pmf_svd_decompose, pmf_svd_rank, pmf_svd_get, pmf_update_w, pmf_update_h, pmf_factorize and
+ *         pmf_frobenius work on the stored entries (see "PCA / SVD" below); W and H are float64 on the device and travel through
+ *         pmf_set_w_* / pmf_get_w_* / pmf_set_h_* / pmf_get_h_*.  pmf_stream_*, pmf_nndsvd_init, pmf_fill_w_uniform,
+ *         pmf_fill_h_uniform, pmf_snapshot_w and pmf_snapshot_h return PMF_EINVAL while CSR data is resident, and say so.  A later
+ *         dense upload releases the sparse arrays and the float64 factors (W and H are then unset). */
 int pmf_set_v_csr_f32(pmf_ctx* ctx, const int64_t* indptr, const int32_t* indices,
                       const float* vals, int64_t nnz);
 int pmf_check_csr(int64_t m, int64_t n, const int64_t* indptr, const int32_t* indices, int64_t nnz);
@@ -384,7 +393,15 @@ int pmf_aa_rounds(pmf_ctx* ctx, int32_t* rounds);
  * that pmf_frobenius is svd.py's ||data - U S V||.
  * pmf_svd_get: U (rows x rank), S (rank values) and V (rank x cols) of the last decomposition as float64, row-major; a NULL
  * pointer skips that factor.  pmf_svd_rank: the rank of that decomposition (what a PCA W step found).  Both return PMF_EINVAL
- * when the resident V has not been decomposed. */
+ * when the resident V has not been decomposed.
+ * On CSR data (pmf_set_v_csr_f32; path "svd_csr") the Gram matrix of the short side comes from the stored entries in exact fixed
+ * point (k_csr_gram on the image of V for rows > cols, on the image of V^T otherwise), the solver, the cut and the order are the
+ * same, and pmf_set_option "svd_num_triples" (0 = all, the default; at most 1024) cuts the kept triples to the leading ones: it
+ * carries SVD's k and PCA's num_bases.  The projected side, PCA's H = W^T V and the cross term of the error are one float64 pass
+ * over the stored entries (k_csr_proj_f64); every factor is float64.  pmf_frobenius is the trace identity
+ * ||V||^2 - 2 <W^T V, H> + <W^T W, H H^T> in float64, clamped at 0 -- behind pmf_svd_decompose with W = U, H = S V, where
+ * pmf_get_w_* / pmf_get_h_* refuse (pmf_svd_get reads the factors).  pmf_update_w with another number of bases than the resident
+ * H has drops that H.  Two runs give the same bits. */
 int pmf_svd_decompose(pmf_ctx* ctx, int32_t* rank);
 int pmf_svd_rank(pmf_ctx* ctx, int32_t* rank);
 int pmf_svd_get(pmf_ctx* ctx, double* U, double* S, double* V);

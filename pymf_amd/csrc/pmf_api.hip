@@ -47,6 +47,7 @@
 #include "pmf_svd.h"
 #include "pmf_cur.h"
 #include "pmf_cur_csr.h"
+#include "pmf_svd_csr.h"
 #include "pmf_lev.h"
 #include "pmf_greedy.h"
 
@@ -72,6 +73,7 @@
 #include "pmf_host_aa.h"
 #include "pmf_host_svd.h"
 #include "pmf_host_cur_csr.h"
+#include "pmf_host_svd_csr.h"
 #include "pmf_host_cur.h"
 #include "pmf_host_greedy.h"
 #include "pmf_host_factorize.h"
@@ -165,7 +167,9 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
     const int nslabs = std::max(c->nchunks, c->fused_wgs);
     // dV [mp][np] is allocated by the first pmf_set_v_dense_f32 / pmf_fill_v_uniform: CSR and
     // streamed (pmf_stream_*) contexts never hold a dense V
-    PMFCHK(dalloc(c, &c->dW, (size_t)c->mp * c->KP));
+    // (a PCA / SVD context allocates its row-count sized float32 buffers -- dW, dW1, dW2 -- with the first dense data or
+    // float32-path W: ensure_wbufs.  On CSR data they are never read, and each is the size of the dense image)
+    if (algo != PMF_ALGO_PCA) PMFCHK(dalloc(c, &c->dW, (size_t)c->mp * c->KP));
     PMFCHK(dalloc(c, &c->dH, (size_t)c->KP * c->np));
     PMFCHK(dalloc(c, &c->dG, (size_t)c->KP * c->KP));
     PMFCHK(dalloc(c, &c->dGd, (size_t)c->KP * c->KP));
@@ -176,8 +180,10 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
       PMFCHK(dalloc(c, &c->dSlab, (size_t)nslabs * ps_elems(c)));
     } else {                    // one 128-base block at a time: [chunk][128][max(np, KP) + 128]
       PMFCHK(dalloc(c, &c->dSlab, (size_t)c->nchunks * 128 * (std::max(c->np, c->KP) + 128)));
-      PMFCHK(dalloc(c, &c->dW1, (size_t)std::max<int64_t>(c->mp, c->np) * c->KP));
-      PMFCHK(dalloc(c, &c->dW2, (size_t)c->mp * c->KP));
+      if (algo != PMF_ALGO_PCA) {
+        PMFCHK(dalloc(c, &c->dW1, (size_t)std::max<int64_t>(c->mp, c->np) * c->KP));
+        PMFCHK(dalloc(c, &c->dW2, (size_t)c->mp * c->KP));
+      }
     }
     c->dpart_cap = std::max<int64_t>(std::max<int64_t>(c->mp / 64, 1024), c->np / 8 + 2);
     PMFCHK(dalloc(c, &c->dPart, (size_t)c->dpart_cap));
@@ -190,7 +196,7 @@ int pmf_ctx_create(pmf_ctx** out, int32_t algo, int64_t m_local, int64_t n, int3
     PMFCHK(dalloc(c, &c->dFerr, (size_t)c->ferr_cap));
     if (algo == PMF_ALGO_RNMF) PMFCHK(dalloc(c, &c->dD, (size_t)c->mp * c->np));
     if (algo != PMF_ALGO_NMF && algo != PMF_ALGO_CNMF && !cluster) {
-      if (!c->dW1) PMFCHK(dalloc(c, &c->dW1, (size_t)std::max<int64_t>(c->mp, c->np) * c->KP));
+      if (!c->dW1 && algo != PMF_ALGO_PCA) PMFCHK(dalloc(c, &c->dW1, (size_t)std::max<int64_t>(c->mp, c->np) * c->KP));
       PMFCHK(dalloc(c, &c->dGinvT, (size_t)c->KP * c->KP));
     }
     if (algo == PMF_ALGO_SNMF) {
@@ -277,6 +283,8 @@ static int set_v_dense(pmf_ctx* c, const void* V, bool f64, int64_t ld, const ch
   HIPCHK(c, hipSetDevice(c->device));
   PMFCHK(sivm_csc_left(c));
   PMFCHK(cur_csr_left(c));
+  PMFCHK(svd_csr_left(c));
+  PMFCHK(ensure_wbufs(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
   PMFCHK(f64 ? upload_rows(c, c->dV, c->np, static_cast<const double*>(V), ld, c->m, c->n)
@@ -296,7 +304,8 @@ int pmf_set_v_csr_f32(pmf_ctx* c, const int64_t* indptr, const int32_t* indices,
     return fail(c, PMF_EINVAL, "pmf_set_v_csr_f32: bad arguments");
   if (c->algo == PMF_ALGO_NMF) return nmf_csr_set_v(c, indptr, indices, vals, nnz);
   if (c->algo == PMF_ALGO_CUR) return cur_csr_set_v(c, indptr, indices, vals, nnz);
-  if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF, NMF and CUR / CMD");
+  if (c->algo == PMF_ALGO_PCA) return svd_csr_set_v(c, indptr, indices, vals, nnz);
+  if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF, NMF, CUR / CMD and PCA / SVD");
   // refused arrays never reach the device: what is resident stays as it was
   if (const char* why = csr_check(c->m, c->n, indptr, indices, nnz)) return fail(c, PMF_EINVAL, std::string("pmf_set_v_csr_f32: ") + why);
   HIPCHK(c, hipSetDevice(c->device));
@@ -358,6 +367,8 @@ int pmf_fill_v_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   if (!c) return PMF_EINVAL;
   PMFCHK(sivm_csc_left(c));
   PMFCHK(cur_csr_left(c));
+  PMFCHK(svd_csr_left(c));
+  PMFCHK(ensure_wbufs(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
   PMFCHK(fill(c, c->dV, c->np, c->m, c->n, row0, seed));
@@ -369,6 +380,8 @@ int pmf_fill_v_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
 }
 int pmf_fill_w_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   if (!c) return PMF_EINVAL;
+  PMFCHK(svd_csr_refuse(c, "pmf_fill_w_uniform"));
+  PMFCHK(ensure_wbufs(c));
   PMFCHK(w_pipe_join(c));        // (a pipelined W = V M write still in flight on the side stream must not land on the new W)
   PMFCHK(fill(c, c->dW, c->KP, c->m, c->k, row0, seed));
   w_replaced(c, /*by_caller=*/true);
@@ -376,6 +389,7 @@ int pmf_fill_w_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
 }
 int pmf_fill_h_uniform(pmf_ctx* c, uint64_t seed) {
   if (!c) return PMF_EINVAL;
+  PMFCHK(svd_csr_refuse(c, "pmf_fill_h_uniform"));
   PMFCHK(fill(c, c->dH, c->np, c->k, c->n, 0, seed));
   h_replaced(c, false, true);
   return PMF_OK;
@@ -396,6 +410,8 @@ static int zero_padding(pmf_ctx* c, float* buf, int64_t ld, int64_t rows_total, 
 static int set_w(pmf_ctx* c, const void* W, bool f64, const char* who) {
   if (!c || !W) return fail(c, PMF_EINVAL, std::string(who) + ": bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
+  if (svd_csr(c)) return svd_csr_set_w(c, W, f64);
+  PMFCHK(ensure_wbufs(c));
   PMFCHK(w_pipe_join(c));
   PMFCHK(zero_padding(c, c->dW, c->KP, c->mp, c->m, c->k));
   PMFCHK(f64 ? upload_rows(c, c->dW, c->KP, static_cast<const double*>(W), c->k, c->m, c->k)
@@ -408,12 +424,14 @@ int pmf_set_w_f64(pmf_ctx* c, const double* W) { return set_w(c, W, true, "pmf_s
 int pmf_get_w_f64(pmf_ctx* c, double* W) {
   PMFCHK(need(c, false, true, false));
   if (!W) return fail(c, PMF_EINVAL, "W is NULL");
+  if (svd_csr(c)) return svd_csr_get_w(c, W);
   PMFCHK(materialize_w(c));
   return download_rows<double>(c, W, c->dW, c->KP, c->m, c->k);
 }
 int pmf_set_h_f64(pmf_ctx* c, const double* H) {
   if (!c || !H) return fail(c, PMF_EINVAL, "pmf_set_h_f64: bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
+  if (svd_csr(c)) return svd_csr_set_h(c, H, true);
   PMFCHK(zero_padding(c, c->dH, c->np, c->KP, c->k, c->n));
   PMFCHK(upload_rows<double>(c, c->dH, c->np, H, c->n, c->k, c->n));
   h_replaced(c, false, true);      // (here already: if the float64 copy below fails, Hd is widened anew from this H)
@@ -434,6 +452,7 @@ int pmf_set_h_f64(pmf_ctx* c, const double* H) {
 int pmf_get_h_f64(pmf_ctx* c, double* H) {
   PMFCHK(need(c, false, false, true));
   if (!H) return fail(c, PMF_EINVAL, "H is NULL");
+  if (svd_csr(c)) return svd_csr_get_h(c, H);
   PMFCHK(nmf_csr_sync_h(c));
   if (h_in_f64(c) && c->dHd) {     // SNMF: the float64 H the device iterates on (entries another writer of the float32 H replaced: widened)
     PMFCHK(ensure_hd(c));
@@ -451,12 +470,14 @@ int pmf_get_h_f64(pmf_ctx* c, double* H) {
 int pmf_get_w_f32(pmf_ctx* c, float* W) {
   PMFCHK(need(c, false, true, false));
   if (!W) return fail(c, PMF_EINVAL, "W is NULL");
+  if (svd_csr(c)) return svd_csr_get_w(c, W);
   PMFCHK(materialize_w(c));
   return download_padded(c, W, c->k, c->dW, c->KP, c->m, c->k);
 }
 int pmf_set_h_f32(pmf_ctx* c, const float* H) {
   if (!c || !H) return fail(c, PMF_EINVAL, "pmf_set_h_f32: bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
+  if (svd_csr(c)) return svd_csr_set_h(c, H, false);
   PMFCHK(zero_padding(c, c->dH, c->np, c->KP, c->k, c->n));
   PMFCHK(upload_padded(c, c->dH, c->np, H, c->n, c->k, c->n));
   h_replaced(c, false, true);
@@ -465,6 +486,7 @@ int pmf_set_h_f32(pmf_ctx* c, const float* H) {
 int pmf_get_h_f32(pmf_ctx* c, float* H) {
   PMFCHK(need(c, false, false, true));
   if (!H) return fail(c, PMF_EINVAL, "H is NULL");
+  if (svd_csr(c)) return svd_csr_get_h(c, H);
   PMFCHK(nmf_csr_sync_h(c));
   return download_padded(c, H, c->n, c->dH, c->np, c->k, c->n);
 }
@@ -757,6 +779,7 @@ int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (c) c->hd_synced = false;
   if (!c) return PMF_EINVAL;
   PMFCHK(cur_csr_refuse(c, "pmf_stream_*"));
+  PMFCHK(svd_csr_refuse(c, "pmf_stream_*"));
   if (!algo_row(c).streamable)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (nmf_csr(c)) return fail(c, PMF_EINVAL, "pmf_stream_*: not on an NMF context that holds CSR data (set dense data, or none, first)");
@@ -946,6 +969,7 @@ int pmf_stream_end(pmf_ctx* c, double* ferr, int32_t* needs_direct) {
 int pmf_nndsvd_init(pmf_ctx* c, int32_t* rank_found) {
   PMFCHK(need(c, true, false, false));
   if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF) return fail(c, PMF_EINVAL, "pmf_nndsvd_init: not for RNMF / CNMF contexts");
+  PMFCHK(svd_csr_refuse(c, "pmf_nndsvd_init"));
   return nndsvd_init(c, rank_found);
 }
 
@@ -1248,6 +1272,13 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
     c->opt_rowgemm_stream = (int)value;
     return PMF_OK;
   }
+  if (std::strcmp(name, "svd_num_triples") == 0) {
+    if (c->algo != PMF_ALGO_PCA) return fail(c, PMF_EINVAL, "svd_num_triples: PCA / SVD contexts only");
+    if (value < 0 || value > PMF_GRAM_MAX_NP) return fail(c, PMF_EINVAL, "svd_num_triples: 0 (all) .. 1024");
+    if (c->svd_triples != (int)value && c->v_csr) c->svd_valid = false;     // (a decomposition of CSR data kept another count)
+    c->svd_triples = (int)value;
+    return PMF_OK;
+  }
   if (std::strcmp(name, "pca_num_bases") == 0) {
     if (c->algo != PMF_ALGO_PCA) return fail(c, PMF_EINVAL, "pca_num_bases: PCA / SVD contexts only");
     if (value < 0 || value > c->k) return fail(c, PMF_EINVAL, "pca_num_bases: 0 (all) .. the context's base count");
@@ -1484,6 +1515,7 @@ int pmf_invalidate_v(pmf_ctx* c) {
 }
 
 int pmf_snapshot_w(pmf_ctx* c) {
+  PMFCHK(svd_csr_refuse(c, "pmf_snapshot_w"));
   PMFCHK(need(c, false, true, false));
   PMFCHK(materialize_w(c));
   if (!c->dWsnap) PMFCHK(dalloc_raw(c, &c->dWsnap, (size_t)c->mp * c->KP));
@@ -1508,6 +1540,7 @@ int pmf_restore_w(pmf_ctx* c) {
 // per-workgroup partial sums the next one-pass launch adds) -- a restored H then continues with the SAME bits of G; the other
 // classes form G from H whenever they need it.
 int pmf_snapshot_h(pmf_ctx* c) {
+  PMFCHK(svd_csr_refuse(c, "pmf_snapshot_h"));
   PMFCHK(need(c, false, false, true));
   const size_t hb = (size_t)c->KP * c->np * sizeof(float), gb = (size_t)c->KP * c->KP * sizeof(float);
   if (!c->dHsnap) PMFCHK(dalloc_raw(c, &c->dHsnap, (hb + gb + (size_t)PMF_HGRAM_MAX_WGS * gb) / sizeof(float)));

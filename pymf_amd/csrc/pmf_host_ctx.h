@@ -216,6 +216,14 @@ struct pmf_ctx {
   bool svd_left = false;        // rows > cols: svd.py's _left_svd
   bool svd_valid = false;       // dSvdE / dSvdS / dSvdP belong to the current V.  <- V
   int pca_bases = 0;            // pmf_set_option("pca_num_bases"): columns of U that PCA's W step takes, 0 = all
+  // SVD / PCA on CSR data (pmf_svd_csr.h, pmf_host_svd_csr.h): v_csr with both CSR images resident and no dV, as on a CUR / CMD
+  // context (cur_ip: the row pointers on the host).  Float64 throughout: the projected side [long side padded][svd_rp], rp = the
+  // kept count rounded up to 64 (V is kept transposed for rows <= cols); PCA's W [mp][svd_wp] and H^T [np][svd_wp] -- dW and dH
+  // are not used while CSR data is resident
+  int svd_triples = 0;          // pmf_set_option("svd_num_triples"): leading triples a decomposition of CSR data keeps, 0 = all above the cut
+  double *dSvdPd = nullptr, *dSvdWd = nullptr, *dSvdHTd = nullptr;
+  int svd_rp = 0, svd_wp = 0;
+  bool svd_fact = false;        // pmf_svd_decompose ran last: the factors of pmf_frobenius are W = U, H = S V of dSvdE / dSvdPd.  <- V, W, H
   // CUR / CMD (pmf_cur.h): the unscaled gathers Cg [mp][round_up(nc, 64)] and Rg [round_up(nr, 64)][np] of the last pmf_cur_compute;
   // on the host sqrt(ccnt), sqrt(rcnt) and the middle factor U [nc][nr]
   float *dCurCg = nullptr, *dCurRg = nullptr;
@@ -380,6 +388,17 @@ int dgrow(pmf_ctx* c, T** p, int64_t* cap, int64_t count, size_t per = 1, bool s
 static inline bool use_csr(const pmf_ctx* c) { return c->v_csr && !c->csr_dense; }
 // NMF on CSR data: both half steps are k_nmf_sp_step (pmf_host_nmf_csr.h)
 static inline bool nmf_csr(const pmf_ctx* c) { return c->algo == PMF_ALGO_NMF && use_csr(c); }
+
+// PCA / SVD contexts: the float32 factor W and the two scratch arrays of its shape, [rows padded][KP] each -- as large as the dense
+// image when the context is as wide as the short side.  Allocated by the entry points that bring dense data or a float32-path W
+// (pmf_set_v_dense_*, pmf_fill_v_uniform, pmf_set_w_*, pmf_fill_w_uniform), never while the context only ever holds CSR data.
+int ensure_wbufs(pmf_ctx* c) {
+  if (c->algo != PMF_ALGO_PCA) return PMF_OK;
+  if (!c->dW) PMFCHK(dalloc(c, &c->dW, (size_t)c->mp * c->KP));
+  if (!c->dW1) PMFCHK(dalloc(c, &c->dW1, (size_t)std::max<int64_t>(c->mp, c->np) * c->KP));
+  if (c->nb > 1 && !c->dW2) PMFCHK(dalloc(c, &c->dW2, (size_t)c->mp * c->KP));
+  return PMF_OK;
+}
 
 int ensure_dv(pmf_ctx* c) {
   if (c->dV) return PMF_OK;

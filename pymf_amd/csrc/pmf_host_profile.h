@@ -68,6 +68,11 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.flops = 2.0 * m * n * q;                                   // the whole Gram matrix ...
     st.exec_flops = m * n * (q + 64.0);                           // ... of which the upper block triangle is formed
     st.bytes = 4.0 * (double)c->mp * (double)c->np;              // V once
+    if (c->v_csr) {                                               // the projection pass: svd_csr_proj writes the figures of the launch
+      st.name = "k_csr_proj_f64";
+      st.flops = st.exec_flops = 2.0 * nnz * 64.0;
+      st.bytes = 12.0 * nnz + 8.0 * (double)(c->m > c->n ? c->mp : (int64_t)c->np) * 65.0;
+    }
   } else if (c->algo == PMF_ALGO_CUR && c->opt_profile_cur == 1) {
     st.site = SITE_CUR_LEV;                                       // the long-side leverage pass: cur_leverage writes the instantiation's name
     st.name = "k_lev_f64";                                        // and the flops and bytes of the call (they depend on its k)

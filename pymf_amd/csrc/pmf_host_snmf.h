@@ -188,6 +188,54 @@ int snmf_fused_iteration(pmf_ctx* c) {
   return h_step_from_ps(c);
 }
 
+// out [np][np] float64 = the Gram matrix of the columns of a CSR image (indptr [>= lines + 1], indices < np, vals; nnz entries in
+// `lines` lines): k_csr_gram's per-workgroup images in exact fixed point (pmf_csr.h), added up as integers.  np is a multiple of
+// 64; the slabs and the word of the largest |v| stay with the context (one image width per context).
+int csr_gram_f64(pmf_ctx* c, const int64_t* indptr, const int32_t* indices, const float* vals, int64_t nnz, int64_t lines, int np,
+                 double* out) {
+  const size_t E = (size_t)np * np;
+  const size_t T2 = 2 * gram_tri(np);                                // two 64-bit limbs per entry of the upper triangle
+  const int use_lds = T2 * sizeof(unsigned long long) + gram_stage_bytes() <= 160 * 1024;
+  const int wgs = use_lds ? 256 : 32;            // global images are T2 words each: fewer of them
+  // the grids of the two limbs from the largest |v|: |v| < 2^e  ->  u1 = 2^(2e-32), u2 = 2^(2e-64)
+  if (!c->dVmaxBits) PMFCHK(dalloc(c, &c->dVmaxBits, (size_t)1));
+  unsigned* mxbits = c->dVmaxBits;
+  HIPCHK(c, hipMemsetAsync(mxbits, 0, sizeof(unsigned), c->stream));
+  if (nnz > 0) {
+    hipLaunchKernelGGL(k_absmax_bits_f32, dim3((unsigned)std::min<int64_t>((nnz + 255) / 256, 2048)), dim3(256), 0, c->stream, vals, nnz, mxbits);
+    HIPCHK(c, hipGetLastError());
+  }
+  unsigned hb = 0;
+  HIPCHK(c, hipMemcpyAsync(&hb, mxbits, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float vmax;
+  std::memcpy(&vmax, &hb, sizeof(float));
+  const int finite = std::isfinite(vmax) ? 1 : 0;
+  int ex = 0;
+  if (finite && vmax > 0.f) (void)std::frexp(vmax, &ex);             // vmax = f 2^ex, f in [0.5, 1): |v| < 2^ex
+  GramScale gs;
+  gs.u1 = std::ldexp(1.0, 2 * ex - 32); gs.inv_u1 = std::ldexp(1.0, 32 - 2 * ex); gs.inv_u2 = std::ldexp(1.0, 64 - 2 * ex);
+  // per-workgroup images of C: kept with the context (34 MiB at n = 128); zeroed only where the kernel adds
+  // into them directly (LDS images are written out whole)
+  if (!c->dCslabs) PMFCHK(dalloc_raw(c, &c->dCslabs, (size_t)wgs * T2));   // (64-bit limbs)
+  unsigned long long* slabs = reinterpret_cast<unsigned long long*>(c->dCslabs);
+  if (!use_lds) HIPCHK(c, hipMemsetAsync(slabs, 0, (size_t)wgs * T2 * sizeof(unsigned long long), c->stream));
+  const size_t smem = (use_lds ? T2 * sizeof(unsigned long long) : 0) + gram_stage_bytes();
+  static bool attr_done_dev[PMF_MAX_DEVICES] = {};
+  bool& attr_done = attr_done_dev[pmf_current_device()];
+  if (!attr_done) {
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_csr_gram), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(160 * 1024)));
+    attr_done = true;
+  }
+  hipLaunchKernelGGL(k_csr_gram, dim3((unsigned)wgs), dim3(64 * GRAM_WAVES), smem, c->stream, indptr, indices, vals, lines, np, slabs,
+                     use_lds, gs);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_csr_gram_sum, dim3((unsigned)((E + 63) / 64)), dim3(256), 0, c->stream, slabs, wgs, np, out, gs, finite);
+  HIPCHK(c, hipGetLastError());
+  return PMF_OK;
+}
+
 // ---- SNMF in Gram space ---------------------------------------------------------------------------
 // snmf.py:67-70 makes W a LINEAR function of the data once H is given: W = V M, M = H^T inv(H H^T).
 // Everything update_h (snmf.py:72-91) takes from W are XW = V^T W and WW = W^T W, i.e.
@@ -205,48 +253,9 @@ int ensure_vgram(pmf_ctx* c) {
   if (!c->dC) PMFCHK(dalloc(c, &c->dC, (size_t)np * np));
   if (!c->dMTd) PMFCHK(dalloc(c, &c->dMTd, (size_t)c->KP * np));
   if (!c->dPd) PMFCHK(dalloc(c, &c->dPd, (size_t)c->KP * np));
-  if (use_csr(c)) {                 // k_csr_gram: per-workgroup images of C in exact fixed point (pmf_csr.h), added up as integers
+  if (use_csr(c)) {
     const size_t E = (size_t)np * np;
-    const size_t T2 = 2 * gram_tri(np);                                // two 64-bit limbs per entry of the upper triangle
-    const int use_lds = T2 * sizeof(unsigned long long) + gram_stage_bytes() <= 160 * 1024;
-    const int wgs = use_lds ? 256 : 32;            // global images are T2 words each: fewer of them
-    // the grids of the two limbs from the largest |v|: |v| < 2^e  ->  u1 = 2^(2e-32), u2 = 2^(2e-64)
-    if (!c->dVmaxBits) PMFCHK(dalloc(c, &c->dVmaxBits, (size_t)1));
-    unsigned* mxbits = c->dVmaxBits;
-    HIPCHK(c, hipMemsetAsync(mxbits, 0, sizeof(unsigned), c->stream));
-    const int64_t nnz = c->nnz;
-    if (nnz > 0) {
-      hipLaunchKernelGGL(k_absmax_bits_f32, dim3((unsigned)std::min<int64_t>((nnz + 255) / 256, 2048)), dim3(256), 0, c->stream, c->dVals, nnz, mxbits);
-      HIPCHK(c, hipGetLastError());
-    }
-    unsigned hb = 0;
-    HIPCHK(c, hipMemcpyAsync(&hb, mxbits, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float vmax;
-    std::memcpy(&vmax, &hb, sizeof(float));
-    const int finite = std::isfinite(vmax) ? 1 : 0;
-    int ex = 0;
-    if (finite && vmax > 0.f) (void)std::frexp(vmax, &ex);             // vmax = f 2^ex, f in [0.5, 1): |v| < 2^ex
-    GramScale gs;
-    gs.u1 = std::ldexp(1.0, 2 * ex - 32); gs.inv_u1 = std::ldexp(1.0, 32 - 2 * ex); gs.inv_u2 = std::ldexp(1.0, 64 - 2 * ex);
-    // per-workgroup images of C: kept with the context (34 MiB at n = 128); zeroed only where the kernel adds
-    // into them directly (LDS images are written out whole)
-    if (!c->dCslabs) PMFCHK(dalloc_raw(c, &c->dCslabs, (size_t)wgs * T2));   // (64-bit limbs)
-    unsigned long long* slabs = reinterpret_cast<unsigned long long*>(c->dCslabs);
-    if (!use_lds) HIPCHK(c, hipMemsetAsync(slabs, 0, (size_t)wgs * T2 * sizeof(unsigned long long), c->stream));
-    const size_t smem = (use_lds ? T2 * sizeof(unsigned long long) : 0) + gram_stage_bytes();
-    static bool attr_done_dev[PMF_MAX_DEVICES] = {};
-    bool& attr_done = attr_done_dev[pmf_current_device()];
-    if (!attr_done) {
-      HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_csr_gram), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(160 * 1024)));
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(k_csr_gram, dim3((unsigned)wgs), dim3(64 * GRAM_WAVES), smem, c->stream, c->dIndptr,
-                       c->dIndices, c->dVals, c->m, np, slabs, use_lds, gs);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_csr_gram_sum, dim3((unsigned)((E + 63) / 64)), dim3(256), 0, c->stream, slabs, wgs, np, c->dC, gs, finite);
-    HIPCHK(c, hipGetLastError());
+    PMFCHK(csr_gram_f64(c, c->dIndptr, c->dIndices, c->dVals, c->nnz, c->m, np, c->dC));
     PMFCHK(allreduce_sum(c, c->dC, E, true));
   } else {
     DevTemps tmp;

@@ -43,22 +43,17 @@ int gram_f64(pmf_ctx* c, const float* X, int64_t ldx, int qp, int inner, bool tr
   return PMF_OK;
 }
 
-// The eigenpairs of the q x q Gram matrix of the float32 G (gram_f64's operand), scaled to diag(d) . diag(d) when d (q values on
-// the device) is given: float64 Gram matrix, float64 Jacobi.  ev = the q + (q & 1) eigenvalues (host), ord = the indices of those
-// > 1e-8 (svd.py:116-117,141-142) in descending order, QT [.][qp] = the eigenvectors by rows (device, in tmp).  Synchronises.
-int gram_eigh(pmf_ctx* c, const float* G, int64_t ldg, int q, int qp, int inner, bool trans, const double* d, DevTemps& tmp,
-              std::vector<double>& ev, std::vector<int>& ord, double** QT) {
+// The eigenpairs of the float64 q x q matrix A [qp][qp] (overwritten): float64 Jacobi.  ev = the q + (q & 1) eigenvalues (host), ord =
+// the indices of those > 1e-8 (svd.py:116-117,141-142) in descending order, QT [.][qp] = the eigenvectors by rows (device, in tmp).
+// Synchronises.  The one place of the cut and the order: the dense and the CSR path both come through here.
+int eigh_kept(pmf_ctx* c, double* A, int q, int qp, DevTemps& tmp, std::vector<double>& ev, std::vector<int>& ord, double** QT) {
   const int nj = q + (q & 1);
-  double *A = nullptr, *A2 = nullptr, *evals = nullptr;
+  double *A2 = nullptr, *evals = nullptr;
   int* info = nullptr;
-  PMFCHK(talloc(c, tmp, &A, (size_t)qp * qp));
   PMFCHK(talloc(c, tmp, &A2, (size_t)qp * qp));
   PMFCHK(talloc(c, tmp, QT, (size_t)qp * qp));
   PMFCHK(talloc(c, tmp, &evals, (size_t)qp));
   PMFCHK(talloc(c, tmp, &info, 2));
-  PMFCHK(gram_f64(c, G, ldg, qp, inner, trans, A, tmp));
-  if (d) hipLaunchKernelGGL(k_cur_scale_sym, dim3((unsigned)((q * q + 255) / 256)), dim3(256), 0, c->stream, A, qp, q, d);
-  HIPCHK(c, hipGetLastError());
   PMFCHK(jacobi_eigh_dev(c, A, A2, *QT, qp, nj, evals, info));
   ev.resize((size_t)nj);
   HIPCHK(c, hipMemcpyAsync(ev.data(), evals, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -70,12 +65,52 @@ int gram_eigh(pmf_ctx* c, const float* G, int64_t ldg, int q, int qp, int inner,
   return PMF_OK;
 }
 
-int svd_alloc(pmf_ctx* c) {
-  if (c->dSvdE) return PMF_OK;
+// The singular values of the kept eigenpairs onto the device (dSvdS), and the kept eigenvectors in that order into dSvdE (and, scaled
+// by 1 / s, into the float32 B when given): r = ord.size() <= KP
+int svd_keep(pmf_ctx* c, const std::vector<double>& ev, std::vector<int>& ord, const double* QT, int q, int qp, DevTemps& tmp, float* B) {
+  const int r = (int)ord.size(), KP = c->KP;
+  if (r > KP) return fail(c, PMF_EINVAL, "SVD: the rank exceeds the context's base count");
+  int* order = nullptr;
+  PMFCHK(talloc(c, tmp, &order, (size_t)KP));
+  std::vector<double> sv((size_t)KP, 0.0);
+  for (int i = 0; i < r; ++i) sv[(size_t)i] = std::sqrt(ev[(size_t)ord[(size_t)i]]);
+  ord.resize((size_t)KP, 0);
+  HIPCHK(c, hipMemcpyAsync(order, ord.data(), (size_t)KP * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->dSvdS, sv.data(), (size_t)KP * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_svd_gather, dim3((unsigned)(((int64_t)KP * qp + 255) / 256)), dim3(256), 0, c->stream, QT, qp, q, r, KP,
+                     (const int*)order, (const double*)c->dSvdS, c->dSvdE, B);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));           // (the host vectors may leave scope)
+  return PMF_OK;
+}
+
+// The eigenpairs of the q x q Gram matrix of the float32 G (gram_f64's operand), scaled to diag(d) . diag(d) when d (q values on
+// the device) is given: float64 Gram matrix, float64 Jacobi.  ev = the q + (q & 1) eigenvalues (host), ord = the indices of those
+// > 1e-8 (svd.py:116-117,141-142) in descending order, QT [.][qp] = the eigenvectors by rows (device, in tmp).  Synchronises.
+int gram_eigh(pmf_ctx* c, const float* G, int64_t ldg, int q, int qp, int inner, bool trans, const double* d, DevTemps& tmp,
+              std::vector<double>& ev, std::vector<int>& ord, double** QT) {
+  double* A = nullptr;
+  PMFCHK(talloc(c, tmp, &A, (size_t)qp * qp));
+  PMFCHK(gram_f64(c, G, ldg, qp, inner, trans, A, tmp));
+  if (d) hipLaunchKernelGGL(k_cur_scale_sym, dim3((unsigned)((q * q + 255) / 256)), dim3(256), 0, c->stream, A, qp, q, d);
+  HIPCHK(c, hipGetLastError());
+  return eigh_kept(c, A, q, qp, tmp, ev, ord, QT);
+}
+
+// SVD / PCA on CSR data: pmf_host_svd_csr.h (further down the include order)
+bool svd_csr(const pmf_ctx* c);
+int svd_csr_decompose(pmf_ctx* c);
+int svd_csr_update_w(pmf_ctx* c);
+int svd_csr_update_h(pmf_ctx* c);
+int svd_csr_error(pmf_ctx* c, double* out);
+int svd_csr_get(pmf_ctx* c, double* U, double* S, double* V);
+
+// (the float32 projected side is the dense path's alone: a decomposition of CSR data allocates the other two)
+int svd_alloc(pmf_ctx* c, bool with_p = true) {
   const bool left = c->m > c->n;
-  PMFCHK(dalloc(c, &c->dSvdE, (size_t)c->KP * (left ? c->np : c->mp)));
-  PMFCHK(dalloc(c, &c->dSvdS, (size_t)c->KP));
-  PMFCHK(dalloc(c, &c->dSvdP, left ? (size_t)c->mp * c->KP : (size_t)c->KP * c->np));
+  if (!c->dSvdE) PMFCHK(dalloc(c, &c->dSvdE, (size_t)c->KP * (left ? c->np : c->mp)));
+  if (!c->dSvdS) PMFCHK(dalloc(c, &c->dSvdS, (size_t)c->KP));
+  if (with_p && !c->dSvdP) PMFCHK(dalloc(c, &c->dSvdP, left ? (size_t)c->mp * c->KP : (size_t)c->KP * c->np));
   return PMF_OK;
 }
 
@@ -93,22 +128,12 @@ int svd_dense(pmf_ctx* c) {
   DevTemps tmp;
   double* QT = nullptr;
   float* B = nullptr;
-  int* order = nullptr;
-  PMFCHK(talloc(c, tmp, &order, (size_t)KP));
   if (left) PMFCHK(talloc(c, tmp, &B, (size_t)KP * qp));
   std::vector<double> ev;
   std::vector<int> ord;
   PMFCHK(gram_eigh(c, c->dV, (int64_t)c->np, q, qp, left ? (int)c->mp : c->np, left, nullptr, tmp, ev, ord, &QT));
   const int r = (int)ord.size();
-  if (r > KP) return fail(c, PMF_EINVAL, "SVD: the rank exceeds the context's base count");
-  std::vector<double> sv((size_t)KP, 0.0);
-  for (int i = 0; i < r; ++i) sv[(size_t)i] = std::sqrt(ev[(size_t)ord[(size_t)i]]);
-  ord.resize((size_t)KP, 0);
-  HIPCHK(c, hipMemcpyAsync(order, ord.data(), (size_t)KP * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->dSvdS, sv.data(), (size_t)KP * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_svd_gather, dim3((unsigned)(((int64_t)KP * qp + 255) / 256)), dim3(256), 0, c->stream, (const double*)QT, qp, q, r, KP,
-                     (const int*)order, (const double*)c->dSvdS, c->dSvdE, B);
-  HIPCHK(c, hipGetLastError());
+  PMFCHK(svd_keep(c, ev, ord, QT, q, qp, tmp, B));
   if (left) {
     PMFCHK(rowgemm<EPI_STORE>(c, c->dV, c->np, c->np, B, c->np, nullptr, nullptr, c->dSvdP));
   } else {
@@ -140,6 +165,7 @@ int svd_load_w(pmf_ctx* c, int kb) {
 
 // pmf_svd_decompose: svd_dense, then W = U and H = S V, so that pmf_frobenius is ||data - U S V|| (svd.py:92-107)
 int svd_decompose(pmf_ctx* c) {
+  if (svd_csr(c)) return svd_csr_decompose(c);
   PMFCHK(svd_dense(c));
   PMFCHK(svd_load_w(c, c->svd_rank));
   const int64_t total = (int64_t)c->KP * c->np;
@@ -153,6 +179,7 @@ int svd_decompose(pmf_ctx* c) {
 // PCA.update_w (pca.py:93-108): W = the leading num_bases columns of U (all of them when num_bases == 0); S is descending
 // already, so pca.py's argsort is the identity
 int pca_update_w(pmf_ctx* c) {
+  if (svd_csr(c)) return svd_csr_update_w(c);
   PMFCHK(svd_dense(c));
   const int kb = c->pca_bases > 0 ? std::min(c->pca_bases, c->svd_rank) : c->svd_rank;
   return svd_load_w(c, kb);
@@ -160,6 +187,7 @@ int pca_update_w(pmf_ctx* c) {
 
 // PCA.update_h (pca.py:90-91): H = W^T data
 int pca_update_h(pmf_ctx* c) {
+  if (svd_csr(c)) return svd_csr_update_h(c);
   PMFCHK(ensure_ps(c));
   HIPCHK(c, hipMemcpy2DAsync(c->dH, (size_t)c->np * sizeof(float), c->dPS, ((size_t)c->np + c->KP) * sizeof(float),
                              (size_t)c->np * sizeof(float), (size_t)c->KP, hipMemcpyDeviceToDevice, c->stream));
@@ -169,6 +197,7 @@ int pca_update_h(pmf_ctx* c) {
 
 // ||data - W H||: the direct residual (a full-rank PCA fits exactly: the trace identity would cancel)
 int pca_error(pmf_ctx* c, double* out) {
+  if (svd_csr(c)) return svd_csr_error(c, out);
   if (c->nb == 1) return frobenius_direct(c, out);
   PMFCHK(resid_bigk(c, false, c->dScal));
   double ss = 0.0;
@@ -180,6 +209,7 @@ int pca_error(pmf_ctx* c, double* out) {
 
 // U (rows x r), S (r) and V (r x cols) of the last svd_dense as float64, row-major; any of them may be null
 int svd_get(pmf_ctx* c, double* U, double* S, double* V) {
+  if (svd_csr(c)) return svd_csr_get(c, U, S, V);
   if (!c->svd_valid) return fail(c, PMF_EINVAL, "pmf_svd_get: no decomposition of the current data (pmf_svd_decompose / pmf_update_w first)");
   const int r = c->svd_rank, KP = c->KP;
   const int64_t m = c->m, n = c->n;

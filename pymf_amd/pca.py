@@ -8,17 +8,31 @@ SINGULAR values of the selected bases, as in the reference (pca.py:100,108).
 The constructor centres as pca.py:73-82 does: `_data_orig`, `_meanv`, and `data = _data_orig - _meanv` in NumPy; the
 centred array is what goes to the device.  init_w and init_h do nothing; factorize() always runs one iteration.
 
-Supported: dense data, resident, one rank, min(rows, cols) <= 2432, num_bases <= 2432.  scipy.sparse data raises
-TypeError, streamed data (stream_rows) ValueError, a multi-rank world NotImplementedError.
+scipy.sparse data (opt-in: `mdl.accept_sparse = True`) with center_mean=False only: the centred data are dense (the reference
+itself densifies there), so with center_mean=True factorize, update_w, update_h and frobenius_norm raise CentredSparseError: a
+ValueError (center_mean=False is the value that works) that is also the TypeError such data raised before.  The switch is read
+from the object, as SVD's.  The data
+stay sparse on the device (pymf_amd.SVD's sparse path): only the leading num_bases triples are projected, W, H and
+the error are float64 (H = W^T data over the stored entries, the error by the trace identity).  A W step that takes another
+number of bases than the resident H has drops that H.  Limits there: min(rows, cols) <= 1024 after padding to 64.
+
+Supported: dense data, resident, one rank, min(rows, cols) <= 2432, num_bases <= 2432; scipy.sparse data only as described
+above.  Without that opt-in scipy.sparse data raises TypeError; streamed data (stream_rows) ValueError, a multi-rank world
+NotImplementedError (on sparse data ValueError).
 """
 import numpy as np
 
 from . import _lib
 from . import dist as _dist
 from .nmf import NMF, _is_sparse
-from .svd import MAX_RANK
+from .svd import MAX_RANK, canonical_csr, check_sparse_limits
 
-__all__ = ["PCA"]
+__all__ = ["PCA", "CentredSparseError"]
+
+
+class CentredSparseError(TypeError, ValueError):
+    """PCA with center_mean=True on scipy.sparse data: the data are not taken as they are (TypeError, as without the flag), and
+    center_mean=False is the argument value under which they are (ValueError)."""
 
 
 class _WideFactors(object):
@@ -72,6 +86,7 @@ class PCA(NMF):
     """
     _SHIPPED = True
     _ALGO = _lib.ALGO_PCA
+    accept_sparse = False     # opt-in, per object: scipy.sparse data stays sparse on the device (center_mean=False only; module docstring)
     _NITER = 1                                                 # pca.py:133
     _SKIP_MISSING_FACTORS = True                               # update_w needs neither factor, update_h no H (both are written whole)
 
@@ -88,7 +103,11 @@ class PCA(NMF):
     def _check_supported(self):
         name = type(self).__name__
         if _is_sparse(self.data):
-            raise TypeError("%s: scipy.sparse data is not supported (dense data only)" % name)
+            if not self._sparse_run():
+                raise TypeError("%s: scipy.sparse data is not supported (dense data only)" % name)
+            if self._center_mean:
+                raise CentredSparseError("%s on scipy.sparse data: the centred data are dense; pass center_mean=False" % name)
+            check_sparse_limits(name, self._data_dimension, self._num_samples, self._world().size)
         if self.stream_rows or self._stream_rows():
             raise ValueError("%s: streamed data (stream_rows) is not supported: the Gram matrix needs the data resident" % name)
         if self._world().size > 1:
@@ -96,11 +115,22 @@ class PCA(NMF):
         if min(self._data_dimension, self._num_samples) > MAX_RANK or self._num_bases > MAX_RANK:
             raise ValueError("%s: min(rows, cols) and num_bases beyond %d are not supported" % (name, MAX_RANK))
 
+    def _sparse_run(self):
+        """`data` is a scipy.sparse matrix and this object takes it (accept_sparse; PCA itself, not its subclasses)."""
+        return bool(self.__dict__.get("accept_sparse", False)) and type(self)._ALGO == _lib.ALGO_PCA and _is_sparse(self.data)
+
+    def _upload_sparse(self, ctx):
+        self._check_supported()
+        csr = canonical_csr(self.data)
+        self._warn_if_float64(csr.data)
+        ctx.set_v_csr(csr.indptr.astype(np.int64), csr.indices.astype(np.int32), csr.data.astype(np.float32))
+
     def _context(self):
         if self._ctx is None:
             k = max(min(self._data_dimension, self._num_samples), self._num_bases, 1)
             ctx = _dist.make_context(self._ALGO, self._data_dimension, self._num_samples, k)
             ctx.set_option("pca_num_bases", max(0, self._num_bases))
+            ctx.set_option("svd_num_triples", min(max(0, self._num_bases), 1024))   # (what a decomposition of sparse data keeps)
             self._ctx = _WideFactors(ctx)
         return self._ctx
 
@@ -144,6 +174,10 @@ class PCA(NMF):
 
     def frobenius_norm(self):
         self._check_supported()
+        if self._sparse_run():                                 # (NMF's returns the reference's -123456 sentinel on sparse data)
+            if not (self._has('H') and self._has('W')):
+                return -123456
+            return self._sync_to_device().frobenius()
         return NMF.frobenius_norm(self)
 
     def factorize(self, show_progress=False, compute_w=True, compute_h=True, compute_err=True, niter=1):
