@@ -111,8 +111,8 @@ const char* pmf_last_error(const pmf_ctx* ctx);   /* ctx may be NULL: last creat
 int pmf_set_v_dense_f32(pmf_ctx* ctx, const float* V, int64_t ld);
 /* V as CSR (m_local rows): indptr[m_local+1] int64, indices[nnz] int32, vals[nnz] f32.  Copied.  Semantics: the dense
  * algorithm on the matrix these arrays describe (entries of one (row, column) pair add up); pmf_frobenius and
- * PMF_COMPUTE_ERR refuse CSR data (PCA / SVD contexts excepted, below).  SNMF, NMF, CUR / CMD and PCA / SVD contexts only; every
- * other family returns PMF_EINVAL.
+ * PMF_COMPUTE_ERR refuse CSR data (PCA / SVD and GREEDY contexts excepted, below).  SNMF, NMF, CUR / CMD, PCA / SVD and GREEDY
+ * contexts only; every other family returns PMF_EINVAL.
  * All check the arrays on the host before anything is uploaded (indptr from 0 to nnz and not decreasing, indices in
  * [0, n); the entries of a row may come in any order and repeat): malformed input is PMF_EINVAL and leaves the resident data
  * as it was.  pmf_check_csr: the same check of the arrays alone, for an m x n matrix, without a context or a device (the
@@ -135,7 +135,13 @@ int pmf_set_v_dense_f32(pmf_ctx* ctx, const float* V, int64_t ld);
  *         pmf_frobenius work on the stored entries (see "PCA / SVD" below); W and H are float64 on the device and travel through
  *         pmf_set_w_* / pmf_get_w_* / pmf_set_h_* / pmf_get_h_*.  pmf_stream_*, pmf_nndsvd_init, pmf_fill_w_uniform,
  *         pmf_fill_h_uniform, pmf_snapshot_w and pmf_snapshot_h return PMF_EINVAL while CSR data is resident, and say so.  A later
- *         dense upload releases the sparse arrays and the float64 factors (W and H are then unset). */
+ *         dense upload releases the sparse arrays and the float64 factors (W and H are then unset).
+ *   GREEDY (algo 15): never a dense V.  The checks (strictly ascending columns, one rank, min(rows, cols) padded to 64 at most
+ *         1024), the transposed copy and the release of a resident dense V are PCA / SVD's.  pmf_path_name: "greedy_csr".
+ *         pmf_update_w, pmf_update_h, pmf_factorize (PMF_COMPUTE_ERR included), pmf_frobenius, pmf_greedy_select (either side),
+ *         pmf_sivm_get_select and the factor transfers work on the stored entries (see "GREEDY" below).  pmf_stream_*,
+ *         pmf_nndsvd_init, pmf_fill_w_uniform, pmf_fill_h_uniform, pmf_snapshot_w and pmf_snapshot_h return PMF_EINVAL while CSR
+ *         data is resident, and say so.  A later dense upload releases the sparse arrays and keeps W and H. */
 int pmf_set_v_csr_f32(pmf_ctx* ctx, const int64_t* indptr, const int32_t* indices,
                       const float* vals, int64_t nnz);
 int pmf_check_csr(int64_t m, int64_t n, const int64_t* indptr, const int32_t* indices, int64_t nnz);
@@ -460,7 +466,18 @@ int pmf_cur_leverage(pmf_ctx* ctx, int32_t k_rows, int32_t k_cols, double* row_l
  * scores 0; when every column does, the lowest index not yet chosen is taken.
  * pmf_greedy_select: the selection alone -- nsel <= 64 indices in selection order -- among the columns of V (transposed = 0) or
  * among its rows (transposed = 1: GREEDY on the transposed view, what GREEDYCUR's row selection is), on a GREEDY or a CUR / CMD
- * context.  Both calls share the Gram matrix and its eigenpairs, formed once per V. */
+ * context.  Both calls share the Gram matrix and its eigenpairs, formed once per V.
+ * On CSR data (pmf_set_v_csr_f32 on a GREEDY context; path "greedy_csr"; min(rows, cols) padded to 64 at most 1024) the data stay
+ * sparse through all rounds (the reference's sparse branch, greedy.py:115-141, holds a dense matrix from the second round on).
+ * The Gram matrix of the short side comes from the stored entries in exact fixed point (k_csr_gram); solver, cut and order are
+ * those of dense data.  Where the candidates lie on the long side, a round is k_greedy_csr_pass -- a wave per CSR line of the
+ * image whose lines are the candidates (both images are resident: pmf_greedy_select with transposed = 1 needs no copy), float64
+ * sums of exact products against the staged operand, the same score and guard, one partial per workgroup -- and
+ * k_greedy_step_csr, k_greedy_step with the chosen column read from its CSR line.  Otherwise k_greedy_gram runs as on dense data.
+ * W = V[:, select] is scattered from the image of V^T (k_greedy_csr_gather).  pmf_update_h: H^T = V^T pinv(W)^T in float64, one
+ * k_csr_proj_f64 pass; H stays float64 on the device and is read through pmf_get_h_f64 / pmf_get_h_f32.  pmf_frobenius and the
+ * error of pmf_factorize: the float64 identity ||data||^2 - 2 <W^T data, H> + <W^T W, H H^T>, clamped at 0 before the root.  Two
+ * runs give the same bits.  pmf_profile_enable times k_greedy_csr_pass. */
 int pmf_greedy_select(pmf_ctx* ctx, int32_t transposed, int32_t nsel, int32_t* select);
 
 /* Device time (ms, HIP events on the library's stream) of the last pmf_factorize loop. */

@@ -50,6 +50,7 @@
 #include "pmf_svd_csr.h"
 #include "pmf_lev.h"
 #include "pmf_greedy.h"
+#include "pmf_greedy_csr.h"
 
 // the internal host code, by concern (each header: one anonymous-namespace block; the order is the dependency order)
 #include "pmf_host_ctx.h"
@@ -75,6 +76,7 @@
 #include "pmf_host_cur_csr.h"
 #include "pmf_host_svd_csr.h"
 #include "pmf_host_cur.h"
+#include "pmf_host_greedy_csr.h"
 #include "pmf_host_greedy.h"
 #include "pmf_host_factorize.h"
 #include "pmf_host_algos.h"
@@ -284,6 +286,7 @@ static int set_v_dense(pmf_ctx* c, const void* V, bool f64, int64_t ld, const ch
   PMFCHK(sivm_csc_left(c));
   PMFCHK(cur_csr_left(c));
   PMFCHK(svd_csr_left(c));
+  PMFCHK(greedy_csr_left(c));
   PMFCHK(ensure_wbufs(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
@@ -305,7 +308,8 @@ int pmf_set_v_csr_f32(pmf_ctx* c, const int64_t* indptr, const int32_t* indices,
   if (c->algo == PMF_ALGO_NMF) return nmf_csr_set_v(c, indptr, indices, vals, nnz);
   if (c->algo == PMF_ALGO_CUR) return cur_csr_set_v(c, indptr, indices, vals, nnz);
   if (c->algo == PMF_ALGO_PCA) return svd_csr_set_v(c, indptr, indices, vals, nnz);
-  if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF, NMF, CUR / CMD and PCA / SVD");
+  if (c->algo == PMF_ALGO_GREEDY) return greedy_csr_set_v(c, indptr, indices, vals, nnz);
+  if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF, NMF, CUR / CMD, PCA / SVD and GREEDY");
   // refused arrays never reach the device: what is resident stays as it was
   if (const char* why = csr_check(c->m, c->n, indptr, indices, nnz)) return fail(c, PMF_EINVAL, std::string("pmf_set_v_csr_f32: ") + why);
   HIPCHK(c, hipSetDevice(c->device));
@@ -368,6 +372,7 @@ int pmf_fill_v_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   PMFCHK(sivm_csc_left(c));
   PMFCHK(cur_csr_left(c));
   PMFCHK(svd_csr_left(c));
+  PMFCHK(greedy_csr_left(c));
   PMFCHK(ensure_wbufs(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
@@ -381,6 +386,7 @@ int pmf_fill_v_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
 int pmf_fill_w_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   if (!c) return PMF_EINVAL;
   PMFCHK(svd_csr_refuse(c, "pmf_fill_w_uniform"));
+  PMFCHK(greedy_csr_refuse(c, "pmf_fill_w_uniform"));
   PMFCHK(ensure_wbufs(c));
   PMFCHK(w_pipe_join(c));        // (a pipelined W = V M write still in flight on the side stream must not land on the new W)
   PMFCHK(fill(c, c->dW, c->KP, c->m, c->k, row0, seed));
@@ -390,6 +396,7 @@ int pmf_fill_w_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
 int pmf_fill_h_uniform(pmf_ctx* c, uint64_t seed) {
   if (!c) return PMF_EINVAL;
   PMFCHK(svd_csr_refuse(c, "pmf_fill_h_uniform"));
+  PMFCHK(greedy_csr_refuse(c, "pmf_fill_h_uniform"));
   PMFCHK(fill(c, c->dH, c->np, c->k, c->n, 0, seed));
   h_replaced(c, false, true);
   return PMF_OK;
@@ -453,6 +460,7 @@ int pmf_get_h_f64(pmf_ctx* c, double* H) {
   PMFCHK(need(c, false, false, true));
   if (!H) return fail(c, PMF_EINVAL, "H is NULL");
   if (svd_csr(c)) return svd_csr_get_h(c, H);
+  if (greedy_csr(c) && c->gr_ht_valid) return greedy_csr_get_h(c, H);
   PMFCHK(nmf_csr_sync_h(c));
   if (h_in_f64(c) && c->dHd) {     // SNMF: the float64 H the device iterates on (entries another writer of the float32 H replaced: widened)
     PMFCHK(ensure_hd(c));
@@ -487,6 +495,7 @@ int pmf_get_h_f32(pmf_ctx* c, float* H) {
   PMFCHK(need(c, false, false, true));
   if (!H) return fail(c, PMF_EINVAL, "H is NULL");
   if (svd_csr(c)) return svd_csr_get_h(c, H);
+  if (greedy_csr(c) && c->gr_ht_valid) return greedy_csr_get_h(c, H);
   PMFCHK(nmf_csr_sync_h(c));
   return download_padded(c, H, c->n, c->dH, c->np, c->k, c->n);
 }
@@ -780,6 +789,7 @@ int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   if (!c) return PMF_EINVAL;
   PMFCHK(cur_csr_refuse(c, "pmf_stream_*"));
   PMFCHK(svd_csr_refuse(c, "pmf_stream_*"));
+  PMFCHK(greedy_csr_refuse(c, "pmf_stream_*"));
   if (!algo_row(c).streamable)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (nmf_csr(c)) return fail(c, PMF_EINVAL, "pmf_stream_*: not on an NMF context that holds CSR data (set dense data, or none, first)");
@@ -970,6 +980,7 @@ int pmf_nndsvd_init(pmf_ctx* c, int32_t* rank_found) {
   PMFCHK(need(c, true, false, false));
   if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF) return fail(c, PMF_EINVAL, "pmf_nndsvd_init: not for RNMF / CNMF contexts");
   PMFCHK(svd_csr_refuse(c, "pmf_nndsvd_init"));
+  PMFCHK(greedy_csr_refuse(c, "pmf_nndsvd_init"));
   return nndsvd_init(c, rank_found);
 }
 
@@ -1516,6 +1527,7 @@ int pmf_invalidate_v(pmf_ctx* c) {
 
 int pmf_snapshot_w(pmf_ctx* c) {
   PMFCHK(svd_csr_refuse(c, "pmf_snapshot_w"));
+  PMFCHK(greedy_csr_refuse(c, "pmf_snapshot_w"));
   PMFCHK(need(c, false, true, false));
   PMFCHK(materialize_w(c));
   if (!c->dWsnap) PMFCHK(dalloc_raw(c, &c->dWsnap, (size_t)c->mp * c->KP));
@@ -1541,6 +1553,7 @@ int pmf_restore_w(pmf_ctx* c) {
 // classes form G from H whenever they need it.
 int pmf_snapshot_h(pmf_ctx* c) {
   PMFCHK(svd_csr_refuse(c, "pmf_snapshot_h"));
+  PMFCHK(greedy_csr_refuse(c, "pmf_snapshot_h"));
   PMFCHK(need(c, false, false, true));
   const size_t hb = (size_t)c->KP * c->np * sizeof(float), gb = (size_t)c->KP * c->KP * sizeof(float);
   if (!c->dHsnap) PMFCHK(dalloc_raw(c, &c->dHsnap, (hb + gb + (size_t)PMF_HGRAM_MAX_WGS * gb) / sizeof(float)));

@@ -13,6 +13,7 @@
 //                      column -1, pad columns are not looked at.  Partials [wg], no float atomics.
 //   k_greedy_step      one workgroup, float64: reduces the partials, appends the index, orthogonalises the chosen column against Q
 //                      (classical Gram-Schmidt, twice), deflates B' by the new q and writes the float32 operand of the next round.
+//                      k_greedy_step_csr is the same body with the chosen column read from a CSR line (pmf_greedy_csr.h).
 // Tall A (rows > cols): k_greedy_gram runs all rounds in Gram space on G = A^T A (float64, cols x cols) and its eigenpairs:
 // C' = B'^T A' starts as lambda_a e_a^T, the deflated Gram matrix is never formed -- its diagonal d and the rows in use follow
 // from the pivoted-Cholesky vectors w_s = G'[:, i_s] / sqrt(G'[i_s, i_s]):  score_j = |C'[:, j]|^2 / d_j,
@@ -152,9 +153,15 @@ struct GreedyStepArgs {
   int ldb;
   int m, n, c;
   int nparts, round;
+  // the CSR form (k_greedy_step_csr): the image whose lines are the candidate columns stands in for A and ld
+  const int64_t* indptr;
+  const int32_t* indices;      // row ids < m (the host checks)
+  const float* vals;
 };
 
-__global__ __launch_bounds__(256) void k_greedy_step(const GreedyStepArgs a) {
+// CSR: the chosen column is a line of the image, scattered into the zeroed vector; everything behind the read is one text
+template <bool CSR>
+__device__ __forceinline__ void greedy_step_body(const GreedyStepArgs& a) {
   __shared__ double rv[PMF_GREEDY_MAX_ROWS];    // the chosen column, then its residual against Q
   __shared__ double dots[PMF_GREEDY_MAX_BASES];
   __shared__ double red[4];
@@ -166,7 +173,14 @@ __global__ __launch_bounds__(256) void k_greedy_step(const GreedyStepArgs a) {
   int idx;
   sivm_reduce_partials(a.pscore, a.pidx, a.nparts, a.n, sb, ib, &best, &idx);
   if (tid == 0) { a.select[i] = idx; a.taken[idx] = 1; }
-  for (int r = tid; r < m; r += 256) rv[r] = (double)a.A[(int64_t)r * a.ld + idx];
+  if constexpr (CSR) {
+    for (int r = tid; r < m; r += 256) rv[r] = 0.0;
+    __syncthreads();
+    const int64_t hi = a.indptr[idx + 1];
+    for (int64_t e = a.indptr[idx] + tid; e < hi; e += 256) rv[a.indices[e]] = (double)a.vals[e];
+  } else {
+    for (int r = tid; r < m; r += 256) rv[r] = (double)a.A[(int64_t)r * a.ld + idx];
+  }
   __syncthreads();
   // classical Gram-Schmidt against the i vectors of Q, twice: the dots of a sweep by waves, then one update
   for (int sweep = 0; sweep < 2; ++sweep) {
@@ -215,6 +229,9 @@ __global__ __launch_bounds__(256) void k_greedy_step(const GreedyStepArgs a) {
     a.Op[(int64_t)r * PMF_GREEDY_OPW + s] = (float)b;
   }
 }
+
+__global__ __launch_bounds__(256) void k_greedy_step(const GreedyStepArgs a) { greedy_step_body<false>(a); }
+__global__ __launch_bounds__(256) void k_greedy_step_csr(const GreedyStepArgs a) { greedy_step_body<true>(a); }
 
 // The state in front of the first round.  QT [.][ldq]: eigenvectors of the short-side Gram matrix by rows, order / sv: the c kept
 // ones in descending order and sqrt of their eigenvalues.  wide: B'_a = sv_a e_a (Bp [c][ldb], Op columns 0 .. c-1, the rest of Op

@@ -108,7 +108,7 @@ constexpr AlgoRow kAlgos[] = {
     {"PCA / SVD",        "svd_gram_f64",   false, true,  false, false, false, false, kV,   kVW,  loop_reads_unwritten, pca_update_w,     pca_update_h,     pca_error,        pca_error,        nullptr, pca_limits},
     {},
     {"CUR / CMD",        "cur_cross_f64",  false, true,  false, false, false, false, kV,   kV,   loop_reads_all,       nullptr,          nullptr,          frobenius_direct, nullptr,          "pmf_cur_compute is the decomposition", cur_limits},
-    {"GREEDY",           "greedy_panels",  false, true,  false, false, false, true,  kV,   kVW,  loop_reads_unwritten, greedy_update_w,  greedy_update_h,  frobenius_direct, frobenius_direct, nullptr, greedy_limits},
+    {"GREEDY",           "greedy_panels",  false, true,  false, false, false, true,  kV,   kVW,  loop_reads_unwritten, greedy_update_w,  greedy_update_h,  greedy_error,     greedy_error,     nullptr, greedy_limits},
 };
 constexpr int kAlgoCount = (int)(sizeof(kAlgos) / sizeof(kAlgos[0]));
 static_assert(kAlgoCount == PMF_ALGO_GREEDY + 1, "one row per PMF_ALGO_* number");

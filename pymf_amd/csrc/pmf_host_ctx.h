@@ -246,6 +246,10 @@ struct pmf_ctx {
   std::vector<double> gr_ev;
   std::vector<int> gr_ord;
   bool gr_eig_valid = false;    // they belong to the current V.  <- V
+  // GREEDY on CSR data (pmf_greedy_csr.h, pmf_host_greedy_csr.h): v_csr with both CSR images resident and no dV, as on a CUR / CMD
+  // context; the H step's result as H^T [np][64] float64 -- dH is not written while CSR data is resident
+  double* dGrHTd = nullptr;
+  bool gr_ht_valid = false;     // dGrHTd holds the context's H (off: dH does).  <- H
   double lamb_w = 0.0, lamb_h = 0.0;   // BNMF penalty weights (bnmf.py:84-85,118-119)
   // streamed V (pmf_stream_*): row tiles pass through two device buffers, V is never resident
   float* dTile[2] = {nullptr, nullptr};
@@ -475,6 +479,7 @@ void h_replaced(pmf_ctx* c, bool hd_synced, bool hd_force) {
   c->have_h = true; c->g_valid = c->num_valid = c->trace_ready = false; c->g_parts = 0; c->hd_synced = hd_synced; c->hd_force = hd_force;
   c->cl_err_valid = false;
   c->ht_valid = c->ht_newer = false;
+  c->gr_ht_valid = false;
   if (c->algo == PMF_ALGO_CMEANS) c->cl_sums_valid = false;   // (Kmeans' sums follow the assignment, not H: kmeans.py:82-87)
 }
 void g_replaced(pmf_ctx* c) {        // CNMF

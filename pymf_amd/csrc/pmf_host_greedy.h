@@ -1,5 +1,5 @@
 // pmf_host_greedy.h -- GREEDY / GREEDYCUR: the eigenpairs of the short-side Gram matrix, the rounds of the selection on the data or
-// on its transposed view, H = pinv(W) data (kernels: pmf_greedy.h, pmf_svd.h, pmf_cur.h)
+// on its transposed view, H = pinv(W) data (kernels: pmf_greedy.h, pmf_svd.h, pmf_cur.h); on CSR data: pmf_host_greedy_csr.h
 // Host code of libpymf_hip.so: included by pmf_api.hip (the translation unit) in this order, nothing else includes it.
 #pragma once
 
@@ -23,7 +23,8 @@ int greedy_eig(pmf_ctx* c) {
   PMFCHK(talloc(c, tmp, &A2, (size_t)qp * qp));
   PMFCHK(talloc(c, tmp, &evals, (size_t)qp));
   PMFCHK(talloc(c, tmp, &info, 2));
-  PMFCHK(gram_f64(c, c->dV, (int64_t)c->np, qp, left ? (int)c->mp : c->np, left, c->dGrG, tmp));
+  if (greedy_csr(c)) PMFCHK(greedy_csr_gram(c, left, qp, c->dGrG));
+  else PMFCHK(gram_f64(c, c->dV, (int64_t)c->np, qp, left ? (int)c->mp : c->np, left, c->dGrG, tmp));
   HIPCHK(c, hipMemcpyAsync(A, c->dGrG, (size_t)qp * qp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->dGrQT, 0, (size_t)qp * qp * sizeof(double), c->stream));
   PMFCHK(jacobi_eigh_dev(c, A, A2, c->dGrQT, qp, nj, evals, info));
@@ -70,10 +71,11 @@ int greedy_launch_pass(pmf_ctx* c, const GreedyPassArgs& a, int wgs, int cols_in
   return fail(c, PMF_EINVAL, "GREEDY: the staged operand is wider than 128 columns");
 }
 
-// greedy.py:105-158 for dense data on the resident V (trans: on its transposed view, the rows of V being the columns to choose
+// greedy.py:105-158 on the resident V, dense or (GREEDY contexts) CSR (trans: on its transposed view, the rows of V being the columns to choose
 // from): nsel indices in selection order into dsel (device).  All rounds are enqueued back to back; synchronises at the end.
 int greedy_select(pmf_ctx* c, bool trans, int nsel, int* dsel) {
-  if (c->v_csr || !c->dV) return fail(c, PMF_EINVAL, "GREEDY: dense resident data only");
+  const bool csr = greedy_csr(c);
+  if (!csr && (c->v_csr || !c->dV)) return fail(c, PMF_EINVAL, "GREEDY: dense resident data only");
   if (multi_rank(c)) return fail(c, PMF_EINVAL, "GREEDY: one rank only in this build");
   if (nsel < 1 || nsel > PMF_GREEDY_MAX_BASES) return fail(c, PMF_EINVAL, "GREEDY: 1 <= num_bases <= 64");
   if (std::min<int64_t>(c->m, c->n) > PMF_SVD_MAX_RANK) return fail(c, PMF_EINVAL, "GREEDY: min(rows, cols) > 2432 is not supported by this build");
@@ -107,6 +109,11 @@ int greedy_select(pmf_ctx* c, bool trans, int nsel, int* dsel) {
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_greedy_gram, dim3(1), dim3(1024), 0, c->stream, (const double*)c->dGrG, qp, C, cc, nsel, Cm, d, Wm, dsel, taken);
     HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // the temporaries are released on return
+    return PMF_OK;
+  }
+  if (csr) {                                           // the wide case over stored entries (pmf_host_greedy_csr.h)
+    PMFCHK(greedy_csr_rounds(c, trans, nsel, cc, order, dsv, taken, dsel, tmp));
     HIPCHK(c, hipStreamSynchronize(c->stream));         // the temporaries are released on return
     return PMF_OK;
   }
@@ -164,13 +171,14 @@ int greedy_select_host(pmf_ctx* c, bool trans, int nsel, int32_t* select) {
 int greedy_update_w(pmf_ctx* c) {
   if (!c->dSvSel) PMFCHK(dalloc(c, &c->dSvSel, (size_t)c->KP));
   PMFCHK(greedy_select(c, false, c->k, c->dSvSel));
-  return gather_selected_w(c);
+  return greedy_csr(c) ? greedy_csr_gather_w(c) : gather_selected_w(c);
 }
 
 // GREEDY.update_h (greedy.py:82-86): H = pinv(W) data, pinv(W) = (W^T W)^+ W^T with svd.py's 1e-8 cut on the eigenvalues (float64
 // Gram matrix of the float32 W, float64 Jacobi), rounded once; the k x m by m x n product is the W^T V product of the operand
 // pinv(W)^T, as SVD projects its other side
 int greedy_update_h(pmf_ctx* c) {
+  if (greedy_csr(c)) return greedy_csr_update_h(c);
   if (c->v_csr || !c->dV) return fail(c, PMF_EINVAL, "GREEDY: dense resident data only");
   const int k = c->k, KP = c->KP;
   if (!c->dGrMT) PMFCHK(dalloc(c, &c->dGrMT, (size_t)c->mp * KP));
@@ -204,5 +212,8 @@ int greedy_update_h(pmf_ctx* c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));           // the temporaries are released on return
   return PMF_OK;
 }
+
+// pmf_frobenius and the error behind an iteration: the direct residual on dense data, the trace identity on CSR data
+int greedy_error(pmf_ctx* c, double* out) { return greedy_csr(c) ? greedy_csr_error(c, out) : frobenius_direct(c, out); }
 
 }  // namespace

@@ -94,6 +94,11 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.name = buf;
     st.flops = st.exec_flops = 2.0 * m * n * (2.0 * k - 1.0);     // [B' | Q]^T V
     st.bytes = 4.0 * m * (double)c->np + 9.0 * (double)c->np;    // V once; the norms and the flags of the chosen columns
+    if (c->v_csr) {                                               // the pass over stored entries: greedy_csr_rounds writes the figures of the launch
+      st.name = "k_greedy_csr_pass<2>";
+      st.flops = st.exec_flops = 2.0 * nnz * (2.0 * k - 1.0);
+      st.bytes = 12.0 * nnz + 8.0 * n + 4.0 * 128.0 * m;
+    }
   } else if (c->algo == PMF_ALGO_SNMF && gram) {
     st.site = SITE_MATERIALIZE;                   // the only m-sized kernel of a Gram-space loop: W = V M, once
     if (use_csr(c)) {

@@ -22,11 +22,25 @@ is consumed as in the reference.
 
 Supported: dense data, resident, one rank, num_bases <= 64, min(rows, cols) <= 2432.  scipy.sparse data raises TypeError,
 streamed data (stream_rows) ValueError, a multi-rank world NotImplementedError, more bases or a longer short side ValueError.
+
+scipy.sparse data (opt-in: `mdl.accept_sparse = True`, the switch NMF, CUR and SVD have; GREEDY only -- GREEDYCUR keeps
+refusing).  The matrix is converted once to canonical CSR (tocsr(), duplicates summed, indices sorted, float32 values, stored
+zeros kept) and stays sparse on the device through all rounds: the score above is evaluated on stored entries
+(k_greedy_csr_pass), W is scattered from them, H = pinv(W) data and the error are formed in float64 without a
+dense image.  factorize(), update_w(), update_h() and frobenius_norm() give what the dense run on toarray() gives: `select`,
+bit-exact columns in a dense W of the data's dtype, a dense float64 H, ferr filled (compute_err=True works; NMF's -123456
+sentinel is not used here).  Limits on top of the above: min(rows, cols), padded to 64, at most 1024 (ValueError).
+Deliberate deviations from the reference's sparse branch (greedy.py:115-141): it subtracts a rank-one matrix from the data in
+every round, so its matrix is dense after the first selection -- here the data are never written; W and H come back dense;
+and the `k` argument stays ignored: all eigenpairs of the short side come from the Jacobi solver, where the reference asks
+ARPACK for k = num_bases triples -- the leading num_bases columns of B are the same.  ferr is the float64 identity
+||data||^2 - 2 <W^T data, H> + <W^T W, H H^T>, clamped at 0.
 """
 import numpy as np
 
 from . import _lib
 from .nmf import NMF, _is_sparse
+from .svd import MAX_SPARSE_SIDE, canonical_csr
 
 __all__ = ["GREEDY"]
 
@@ -52,6 +66,8 @@ class GREEDY(NMF):
     _SHIPPED = True
     _ALGO = _lib.ALGO_GREEDY
     _SKIP_MISSING_FACTORS = True                               # update_w needs neither factor, update_h no H (both are written whole)
+    accept_sparse = False     # opt-in, per object: scipy.sparse data stays sparse on the device (module docstring)
+    _TAKES_SPARSE = True      # GREEDY itself; a class without the sparse device path says False
 
     def __init__(self, data, k=-1, num_bases=4):               # greedy.py:75-80
         NMF.__init__(self, data, num_bases=num_bases)
@@ -59,10 +75,23 @@ class GREEDY(NMF):
         if self._k == -1:
             self._k = num_bases
 
+    def _sparse_run(self):
+        """`data` is a scipy.sparse matrix and this object takes it (accept_sparse)."""
+        return bool(self.accept_sparse) and self._TAKES_SPARSE and _is_sparse(self.data)
+
+    def _upload_sparse(self, ctx):
+        self._check_supported()
+        csr = canonical_csr(self.data)
+        self._warn_if_float64(csr.data)
+        ctx.set_v_csr(csr.indptr.astype(np.int64), csr.indices.astype(np.int32), csr.data.astype(np.float32))
+
     def _check_supported(self):
         name = type(self).__name__
         if _is_sparse(self.data):
-            raise TypeError("%s: scipy.sparse data is not supported (dense data only)" % name)
+            if not self._sparse_run():
+                raise TypeError("%s: scipy.sparse data is not supported (dense data only)" % name)
+            if -(-min(self._data_dimension, self._num_samples) // 64) * 64 > MAX_SPARSE_SIDE:
+                raise ValueError("%s on scipy.sparse data: min(rows, cols) > %d (padded to 64) is not supported" % (name, MAX_SPARSE_SIDE))
         if self.stream_rows or self._stream_rows():
             raise ValueError("%s: streamed data (stream_rows) is not supported: the selection needs the data resident" % name)
         if self._world().size > 1:
@@ -79,6 +108,8 @@ class GREEDY(NMF):
         dt = self.data.dtype if np.issubdtype(getattr(self.data, "dtype", np.float64), np.floating) else np.float64
         if dt == np.float32:
             return ctx.get_w().astype(dt, copy=False)
+        if self._sparse_run():                                 # (the caller's values, not their float32 rounding, as on dense data)
+            return np.ascontiguousarray(self.data.tocsc()[:, self.select].toarray()).astype(dt, copy=False)
         return np.ascontiguousarray(np.asarray(self.data[:, :])[:, self.select]).astype(dt, copy=False)
 
     def _take_select(self, ctx):
@@ -108,6 +139,10 @@ class GREEDY(NMF):
 
     def frobenius_norm(self):
         self._check_supported()
+        if self._sparse_run():                                 # (NMF's returns the reference's -123456 sentinel on sparse data)
+            if not (self._has('H') and self._has('W')):
+                return -123456
+            return self._sync_to_device().frobenius()
         return NMF.frobenius_norm(self)
 
     def factorize(self, niter=1, show_progress=False, compute_w=True, compute_h=True, compute_err=True):
