@@ -141,7 +141,14 @@ int pmf_set_v_dense_f32(pmf_ctx* ctx, const float* V, int64_t ld);
  *         pmf_update_w, pmf_update_h, pmf_factorize (PMF_COMPUTE_ERR included), pmf_frobenius, pmf_greedy_select (either side),
  *         pmf_sivm_get_select and the factor transfers work on the stored entries (see "GREEDY" below).  pmf_stream_*,
  *         pmf_nndsvd_init, pmf_fill_w_uniform, pmf_fill_h_uniform, pmf_snapshot_w and pmf_snapshot_h return PMF_EINVAL while CSR
- *         data is resident, and say so.  A later dense upload releases the sparse arrays and keeps W and H. */
+ *         data is resident, and say so.  A later dense upload releases the sparse arrays and keeps W and H.
+ *   Kmeans / Cmeans (algos 6, 8): never a dense V.  The checks (strictly ascending columns, one rank) and the transposed copy are
+ *         CUR / CMD's; a resident dense V and the slabs of the dense pass are released.  pmf_path_name: "cluster_csr".
+ *         pmf_update_w, pmf_update_h, pmf_factorize (PMF_COMPUTE_ERR included), pmf_frobenius, pmf_cluster_get_assigned,
+ *         pmf_cluster_set_assigned and the factor transfers work on the stored entries (see "Kmeans / Cmeans" below).
+ *         pmf_stream_*, pmf_nndsvd_init, pmf_fill_w_uniform, pmf_fill_h_uniform, pmf_snapshot_w and pmf_snapshot_h return
+ *         PMF_EINVAL while CSR data is resident, and say so.  A later dense upload releases the sparse arrays and keeps W, H
+ *         (rounded to float32) and the assignment. */
 int pmf_set_v_csr_f32(pmf_ctx* ctx, const int64_t* indptr, const int32_t* indices,
                       const float* vals, int64_t nnz);
 int pmf_check_csr(int64_t m, int64_t n, const int64_t* indptr, const int32_t* indices, int64_t nnz);
@@ -275,7 +282,17 @@ int pmf_get_g_f64(pmf_ctx* ctx, double* G);
  *   pmf_factorize    nmf.py:182-202: update_w, update_h, ||V - W H||, the convergence rule, under the PMF_COMPUTE_* flags
  *   pmf_frobenius    the direct residual
  * pmf_cluster_get_assigned: the n cluster indices of the last Kmeans H step (or the ones set); pmf_cluster_set_assigned: a
- * caller's assignment (n indices in [0, num_bases)), which the next pmf_update_w uses. */
+ * caller's assignment (n indices in [0, num_bases)), which the next pmf_update_w uses.
+ * On CSR data (pmf_set_v_csr_f32 on a Kmeans / Cmeans context; path "cluster_csr") both steps run on stored entries.  W stays
+ * float32 [mp][KP]; H lives transposed in float64, H^T [np][64 or 128], and the H transfers transpose on the way.
+ * pmf_update_h: k_cluster_csr_assign<NH, algo> -- a wave per sample (a line of the image of V^T), lane <-> centre,
+ * d^2 = |v|^2 - 2 v.w + |w|^2 in float64 from exact products, argmin (lowest index on ties) or memberships, the denominators
+ * as per-workgroup partials added in workgroup order.  pmf_update_w: k_cluster_csr_num<NH, algo> -- a wave per chunk of 512
+ * stored entries of a data row (the chunks follow from indptr alone), Kmeans reading the assignment, Cmeans the rows of H^T --
+ * and k_cluster_csr_finish, which adds a row's chunks in order, divides and rounds once to float32.  pmf_frobenius and the
+ * error of pmf_factorize: Kmeans right behind its own H step sqrt(sum min d^2); otherwise the float64 identity
+ * ||data||^2 - 2 <W^T data, H> + <W^T W, H H^T>, clamped at 0 before the root.  No atomics: two runs give the same bits.
+ * pmf_profile_enable times both kernels; the record names the one launched last. */
 int pmf_cluster_get_assigned(pmf_ctx* ctx, int32_t* assigned);
 int pmf_cluster_set_assigned(pmf_ctx* ctx, const int32_t* assigned);
 

@@ -8,6 +8,9 @@ convergence rule and the truncation of `ferr` are NMF's (nmf.py:116-120,171-202)
 
 Supported: dense data of any shape, resident, one rank, num_bases <= 128.  scipy.sparse data raises TypeError, streamed data
 (stream_rows) ValueError, a multi-rank world NotImplementedError, more than 128 bases ValueError.
+
+scipy.sparse data: opt-in with `mdl.accept_sparse = True`, as for Kmeans (pymf_amd.kmeans): the data stay sparse
+on the device, W and H come back dense, ferr is the float64 trace identity.
 """
 from . import _lib
 from .kmeans import _Clustering

@@ -51,6 +51,7 @@
 #include "pmf_lev.h"
 #include "pmf_greedy.h"
 #include "pmf_greedy_csr.h"
+#include "pmf_cluster_csr.h"
 
 // the internal host code, by concern (each header: one anonymous-namespace block; the order is the dependency order)
 #include "pmf_host_ctx.h"
@@ -77,6 +78,7 @@
 #include "pmf_host_svd_csr.h"
 #include "pmf_host_cur.h"
 #include "pmf_host_greedy_csr.h"
+#include "pmf_host_cluster_csr.h"
 #include "pmf_host_greedy.h"
 #include "pmf_host_factorize.h"
 #include "pmf_host_algos.h"
@@ -287,6 +289,7 @@ static int set_v_dense(pmf_ctx* c, const void* V, bool f64, int64_t ld, const ch
   PMFCHK(cur_csr_left(c));
   PMFCHK(svd_csr_left(c));
   PMFCHK(greedy_csr_left(c));
+  PMFCHK(cluster_csr_left(c));
   PMFCHK(ensure_wbufs(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
@@ -309,7 +312,8 @@ int pmf_set_v_csr_f32(pmf_ctx* c, const int64_t* indptr, const int32_t* indices,
   if (c->algo == PMF_ALGO_CUR) return cur_csr_set_v(c, indptr, indices, vals, nnz);
   if (c->algo == PMF_ALGO_PCA) return svd_csr_set_v(c, indptr, indices, vals, nnz);
   if (c->algo == PMF_ALGO_GREEDY) return greedy_csr_set_v(c, indptr, indices, vals, nnz);
-  if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF, NMF, CUR / CMD, PCA / SVD and GREEDY");
+  if (is_cluster(c)) return cluster_csr_set_v(c, indptr, indices, vals, nnz);
+  if (c->algo != PMF_ALGO_SNMF) return fail(c, PMF_EINVAL, "CSR input is only wired for SNMF, NMF, CUR / CMD, PCA / SVD, GREEDY and Kmeans / Cmeans");
   // refused arrays never reach the device: what is resident stays as it was
   if (const char* why = csr_check(c->m, c->n, indptr, indices, nnz)) return fail(c, PMF_EINVAL, std::string("pmf_set_v_csr_f32: ") + why);
   HIPCHK(c, hipSetDevice(c->device));
@@ -373,6 +377,7 @@ int pmf_fill_v_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   PMFCHK(cur_csr_left(c));
   PMFCHK(svd_csr_left(c));
   PMFCHK(greedy_csr_left(c));
+  PMFCHK(cluster_csr_left(c));
   PMFCHK(ensure_wbufs(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
@@ -387,6 +392,7 @@ int pmf_fill_w_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   if (!c) return PMF_EINVAL;
   PMFCHK(svd_csr_refuse(c, "pmf_fill_w_uniform"));
   PMFCHK(greedy_csr_refuse(c, "pmf_fill_w_uniform"));
+  PMFCHK(cluster_csr_refuse(c, "pmf_fill_w_uniform"));
   PMFCHK(ensure_wbufs(c));
   PMFCHK(w_pipe_join(c));        // (a pipelined W = V M write still in flight on the side stream must not land on the new W)
   PMFCHK(fill(c, c->dW, c->KP, c->m, c->k, row0, seed));
@@ -397,6 +403,7 @@ int pmf_fill_h_uniform(pmf_ctx* c, uint64_t seed) {
   if (!c) return PMF_EINVAL;
   PMFCHK(svd_csr_refuse(c, "pmf_fill_h_uniform"));
   PMFCHK(greedy_csr_refuse(c, "pmf_fill_h_uniform"));
+  PMFCHK(cluster_csr_refuse(c, "pmf_fill_h_uniform"));
   PMFCHK(fill(c, c->dH, c->np, c->k, c->n, 0, seed));
   h_replaced(c, false, true);
   return PMF_OK;
@@ -439,6 +446,7 @@ int pmf_set_h_f64(pmf_ctx* c, const double* H) {
   if (!c || !H) return fail(c, PMF_EINVAL, "pmf_set_h_f64: bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
   if (svd_csr(c)) return svd_csr_set_h(c, H, true);
+  if (cluster_csr(c)) return cluster_csr_set_h(c, H);
   PMFCHK(zero_padding(c, c->dH, c->np, c->KP, c->k, c->n));
   PMFCHK(upload_rows<double>(c, c->dH, c->np, H, c->n, c->k, c->n));
   h_replaced(c, false, true);      // (here already: if the float64 copy below fails, Hd is widened anew from this H)
@@ -461,6 +469,7 @@ int pmf_get_h_f64(pmf_ctx* c, double* H) {
   if (!H) return fail(c, PMF_EINVAL, "H is NULL");
   if (svd_csr(c)) return svd_csr_get_h(c, H);
   if (greedy_csr(c) && c->gr_ht_valid) return greedy_csr_get_h(c, H);
+  if (cluster_csr(c)) return cluster_csr_get_h(c, H);
   PMFCHK(nmf_csr_sync_h(c));
   if (h_in_f64(c) && c->dHd) {     // SNMF: the float64 H the device iterates on (entries another writer of the float32 H replaced: widened)
     PMFCHK(ensure_hd(c));
@@ -486,6 +495,7 @@ int pmf_set_h_f32(pmf_ctx* c, const float* H) {
   if (!c || !H) return fail(c, PMF_EINVAL, "pmf_set_h_f32: bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
   if (svd_csr(c)) return svd_csr_set_h(c, H, false);
+  if (cluster_csr(c)) return cluster_csr_set_h(c, H);
   PMFCHK(zero_padding(c, c->dH, c->np, c->KP, c->k, c->n));
   PMFCHK(upload_padded(c, c->dH, c->np, H, c->n, c->k, c->n));
   h_replaced(c, false, true);
@@ -496,6 +506,7 @@ int pmf_get_h_f32(pmf_ctx* c, float* H) {
   if (!H) return fail(c, PMF_EINVAL, "H is NULL");
   if (svd_csr(c)) return svd_csr_get_h(c, H);
   if (greedy_csr(c) && c->gr_ht_valid) return greedy_csr_get_h(c, H);
+  if (cluster_csr(c)) return cluster_csr_get_h(c, H);
   PMFCHK(nmf_csr_sync_h(c));
   return download_padded(c, H, c->n, c->dH, c->np, c->k, c->n);
 }
@@ -790,6 +801,7 @@ int pmf_stream_begin(pmf_ctx* c, uint32_t flags, int64_t max_tile_rows) {
   PMFCHK(cur_csr_refuse(c, "pmf_stream_*"));
   PMFCHK(svd_csr_refuse(c, "pmf_stream_*"));
   PMFCHK(greedy_csr_refuse(c, "pmf_stream_*"));
+  PMFCHK(cluster_csr_refuse(c, "pmf_stream_*"));
   if (!algo_row(c).streamable)
     return fail(c, PMF_EINVAL, "pmf_stream_*: NMF, BNMF, SNMF and NMFALS contexts");
   if (nmf_csr(c)) return fail(c, PMF_EINVAL, "pmf_stream_*: not on an NMF context that holds CSR data (set dense data, or none, first)");
@@ -981,6 +993,7 @@ int pmf_nndsvd_init(pmf_ctx* c, int32_t* rank_found) {
   if (c->algo == PMF_ALGO_RNMF || c->algo == PMF_ALGO_CNMF) return fail(c, PMF_EINVAL, "pmf_nndsvd_init: not for RNMF / CNMF contexts");
   PMFCHK(svd_csr_refuse(c, "pmf_nndsvd_init"));
   PMFCHK(greedy_csr_refuse(c, "pmf_nndsvd_init"));
+  PMFCHK(cluster_csr_refuse(c, "pmf_nndsvd_init"));
   return nndsvd_init(c, rank_found);
 }
 
@@ -1528,6 +1541,7 @@ int pmf_invalidate_v(pmf_ctx* c) {
 int pmf_snapshot_w(pmf_ctx* c) {
   PMFCHK(svd_csr_refuse(c, "pmf_snapshot_w"));
   PMFCHK(greedy_csr_refuse(c, "pmf_snapshot_w"));
+  PMFCHK(cluster_csr_refuse(c, "pmf_snapshot_w"));
   PMFCHK(need(c, false, true, false));
   PMFCHK(materialize_w(c));
   if (!c->dWsnap) PMFCHK(dalloc_raw(c, &c->dWsnap, (size_t)c->mp * c->KP));
@@ -1554,6 +1568,7 @@ int pmf_restore_w(pmf_ctx* c) {
 int pmf_snapshot_h(pmf_ctx* c) {
   PMFCHK(svd_csr_refuse(c, "pmf_snapshot_h"));
   PMFCHK(greedy_csr_refuse(c, "pmf_snapshot_h"));
+  PMFCHK(cluster_csr_refuse(c, "pmf_snapshot_h"));
   PMFCHK(need(c, false, false, true));
   const size_t hb = (size_t)c->KP * c->np * sizeof(float), gb = (size_t)c->KP * c->KP * sizeof(float);
   if (!c->dHsnap) PMFCHK(dalloc_raw(c, &c->dHsnap, (hb + gb + (size_t)PMF_HGRAM_MAX_WGS * gb) / sizeof(float)));

@@ -99,9 +99,9 @@ constexpr AlgoRow kAlgos[] = {
     {"BNMF",             nullptr,          true,  false, false, false, true,  false, kVWH, kVWH, loop_reads_all,       do_update_w,      do_update_h,      nmf_frobenius,    nullptr,          nullptr, nullptr},
     {"RNMF",             nullptr,          true,  false, false, false, false, false, kVWH, kVWH, loop_reads_all,       do_update_w,      do_update_h,      nmf_frobenius,    nullptr,          nullptr, nullptr},
     {"CNMF",             "cnmf_gram",      false, true,  false, false, false, false, kVWH, kVWH, loop_reads_all,       nullptr,          nullptr,          cnmf_frobenius,   nullptr,          nullptr, cnmf_limits},
-    {"Kmeans / Cmeans",  "cluster_panels", false, true,  false, false, false, false, kVW,  kVW,  loop_reads_all,       cluster_update_w, cluster_update_h, frobenius_direct, cluster_error,    nullptr, cluster_limits},
+    {"Kmeans / Cmeans",  "cluster_panels", false, true,  false, false, false, false, kVW,  kVW,  loop_reads_all,       cluster_update_w, cluster_update_h, cluster_frobenius, cluster_error,   nullptr, cluster_limits},
     {},
-    {"Kmeans / Cmeans",  "cluster_panels", false, true,  false, false, false, false, kVH,  kVW,  loop_reads_all,       cluster_update_w, cluster_update_h, frobenius_direct, cluster_error,    nullptr, cluster_limits},
+    {"Kmeans / Cmeans",  "cluster_panels", false, true,  false, false, false, false, kVH,  kVW,  loop_reads_all,       cluster_update_w, cluster_update_h, cluster_frobenius, cluster_error,   nullptr, cluster_limits},
     {},
     {"SIVM",             "sivm_panels",    false, true,  true,  false, false, false, kV,   kVW,  loop_reads_unwritten, sivm_update_w,    sivm_update_h,    frobenius_direct, frobenius_direct, nullptr, sivm_limits},
     {"AA",               "aa_pricing",     false, true,  true,  true,  false, false, kVH,  kVW,  loop_reads_aa,        aa_update_w,      aa_update_h,      frobenius_direct, frobenius_direct, nullptr, aa_limits},

@@ -8,6 +8,11 @@ namespace {
 // the new ones.  One launch of k_cluster_pass assigns with the current W and leaves the sums that the NEXT update_w divides
 // (cl_sums_valid); an update_w that no pass preceded (H from the caller, Cmeans' random H0) forms the sums alone first.
 inline bool is_cluster(const pmf_ctx* c) { return c->algo == PMF_ALGO_KMEANS || c->algo == PMF_ALGO_CMEANS; }
+// CSR data is resident on the context: the steps and the error of pmf_host_cluster_csr.h (further down the include order)
+inline bool cluster_csr(const pmf_ctx* c) { return is_cluster(c) && c->v_csr; }
+int cluster_csr_update_w(pmf_ctx* c);
+int cluster_csr_update_h(pmf_ctx* c);
+int cluster_csr_error(pmf_ctx* c, double* out);
 
 // contiguous ranges of 64-column panels over at most `cap` workgroups: the panels each owns and how many there are
 // (k_cluster_pass, k_sivm_pass, k_aa_price, k_greedy_pass)
@@ -18,17 +23,17 @@ void panel_partition(int npanels, int cap, int* ppw, int* wgs) {
 }
 
 int cluster_alloc(pmf_ctx* c) {
-  if (c->dClNum) return PMF_OK;
+  if (c->dClNum) return PMF_OK;                    // (released while CSR data is resident: cluster_csr_set_v)
   // a slab of mp x KP floats per workgroup: at most PMF_CL_MAX_WGS of them and 2 GiB in all (few, tall slabs when m >> n)
   const int64_t by_mem = std::max<int64_t>(1, ((int64_t)1 << 31) / (c->mp * c->KP * (int64_t)sizeof(float)));
   panel_partition(c->np / 64, (int)std::min<int64_t>(PMF_CL_MAX_WGS, by_mem), &c->cl_ppw, &c->cl_wgs);
   PMFCHK(dalloc(c, &c->dClNum, (size_t)c->cl_wgs * c->mp * c->KP));
-  PMFCHK(dalloc(c, &c->dClDen, (size_t)c->cl_wgs * c->KP));
-  PMFCHK(dalloc(c, &c->dClErr, (size_t)c->cl_wgs * 2));
-  PMFCHK(dalloc(c, &c->dClWn, (size_t)c->KP));
-  PMFCHK(dalloc(c, &c->dClTot, (size_t)c->KP + 2));
-  PMFCHK(dalloc(c, &c->dClMu, (size_t)c->mp));
-  PMFCHK(dalloc(c, &c->dClAsg, (size_t)c->np));
+  if (!c->dClDen) PMFCHK(dalloc(c, &c->dClDen, (size_t)c->cl_wgs * c->KP));
+  if (!c->dClErr) PMFCHK(dalloc(c, &c->dClErr, (size_t)c->cl_wgs * 2));
+  if (!c->dClWn) PMFCHK(dalloc(c, &c->dClWn, (size_t)c->KP));
+  if (!c->dClTot) PMFCHK(dalloc(c, &c->dClTot, (size_t)c->KP + 2));
+  if (!c->dClMu) PMFCHK(dalloc(c, &c->dClMu, (size_t)c->mp));
+  if (!c->dClAsg) PMFCHK(dalloc(c, &c->dClAsg, (size_t)c->np));
   return PMF_OK;
 }
 
@@ -81,9 +86,10 @@ int cluster_pass(pmf_ctx* c, bool assign) {
   return PMF_OK;
 }
 
-int cluster_update_h(pmf_ctx* c) { return cluster_pass(c, true); }
+int cluster_update_h(pmf_ctx* c) { return cluster_csr(c) ? cluster_csr_update_h(c) : cluster_pass(c, true); }
 
 int cluster_update_w(pmf_ctx* c) {
+  if (cluster_csr(c)) return cluster_csr_update_w(c);
   if (!c->cl_sums_valid) PMFCHK(cluster_pass(c, false));
   const int64_t elems = c->mp * c->KP;
   const dim3 grid((unsigned)((elems + 255) / 256));
@@ -101,6 +107,7 @@ int cluster_update_w(pmf_ctx* c) {
 // ||V - mu||^2 (tight clusters: the expansion has cancelled, the rule of nmf_error / cnmf_error); everything else takes
 // the direct residual
 int cluster_error(pmf_ctx* c, double* out) {
+  if (cluster_csr(c)) return cluster_csr_error(c, out);
   if (!c->cl_err_valid) return frobenius_direct(c, out);
   double t[2] = {0.0, 0.0};                        // sum_c min_j d^2, sum_c ||v_c - mu||^2
   HIPCHK(c, hipMemcpyAsync(t, c->dClTot + c->KP, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -109,5 +116,8 @@ int cluster_error(pmf_ctx* c, double* out) {
   *out = std::sqrt(t[0]);
   return PMF_OK;
 }
+
+// pmf_frobenius: the direct residual on dense data, as before; on CSR data the error of the steps
+int cluster_frobenius(pmf_ctx* c, double* out) { return cluster_csr(c) ? cluster_csr_error(c, out) : frobenius_direct(c, out); }
 
 }  // namespace

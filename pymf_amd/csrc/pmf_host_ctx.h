@@ -172,6 +172,14 @@ struct pmf_ctx {
   bool cl_sums_valid = false;   // the slabs belong to the current V and assignment (Kmeans) / H (Cmeans).  <- V, H (Cmeans), the assignment
   bool cl_mu_valid = false;     // dClMu holds the row means of the current V.  <- V
   bool cl_err_valid = false;    // dClTot[KP] = ||V - W H||^2 of the current V, W, H (Kmeans, right behind its H step).  <- V, W, H
+  // Kmeans / Cmeans on CSR data (pmf_cluster_csr.h, pmf_host_cluster_csr.h): v_csr with both CSR images resident and no dV, as on a
+  // CUR / CMD context.  H lives as H^T [np][cc_ld] float64 (dH is not used while CSR data is resident); |v|^2 of the rows [mp] and
+  // behind them of the samples [np]; the chunks of the data rows (cc_chunks of them: the first chunk of every row [mp + 1], the row
+  // of every chunk) with their partial sums [cc_chunks][cc_ld]; the partials of the denominators and of the error per workgroup
+  // of the H step, their totals [cc_ld + 2], |w_c|^2 [cc_ld].  dClAsg and the cl_* flags are shared with the dense path.
+  double *dCcHT = nullptr, *dCcSq = nullptr, *dCcPart = nullptr, *dCcDen = nullptr, *dCcErr = nullptr, *dCcTot = nullptr, *dCcWn = nullptr;
+  int *dCcChunkOff = nullptr, *dCcChunkRow = nullptr;
+  int cc_ld = 0, cc_chunks = 0, cc_wgs = 0, cc_lpw = 0;
   // SIVM (pmf_sivm.h): the recurrence's state ([3][np] float64), the two partials arrays of the argmax (scores, indices), select,
   // (maxd, a); H step: the right-hand sides f + lambda [KP][np], the brackets [6][np], their sides, unfinished columns per round
   double *dSvState = nullptr, *dSvPart = nullptr, *dSvScal = nullptr, *dSvLam = nullptr;

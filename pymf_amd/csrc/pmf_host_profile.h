@@ -24,6 +24,12 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
     st.name = buf;
     st.flops = st.exec_flops = 4.0 * m * n * k;                  // W^T V and V H^T
     st.bytes = 4.0 * (m * n + k * n + 2.0 * m * k);              // V once, H written, W read, the sums written
+    if (c->v_csr) {                                               // the two passes over stored entries: cluster_csr_update_h / _w write the
+      snprintf(buf, sizeof(buf), "k_cluster_csr_assign<%d,%s>", c->k <= 64 ? 1 : 2, c->algo == PMF_ALGO_KMEANS ? "kmeans" : "cmeans");
+      st.name = buf;                                              // name and the figures of the launch at hand
+      st.flops = st.exec_flops = 2.0 * nnz * k;
+      st.bytes = 8.0 * nnz + 16.0 * n + 8.0 * (c->k <= 64 ? 64.0 : 128.0) * n;
+    }
   } else if (c->algo == PMF_ALGO_SIVM && c->sv_sgreedy) {
     st.site = SITE_SGREEDY;
     st.name = "k_sgreedy_pass";

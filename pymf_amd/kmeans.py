@@ -12,6 +12,16 @@ The draw of the initial centres is the reference's: `random.sample(range(num_sam
 Supported: dense data of any shape, resident, one rank, num_bases <= 128.  scipy.sparse data raises TypeError, streamed data
 (stream_rows) ValueError, a multi-rank world NotImplementedError, more than 128 bases ValueError.  update_w() before any
 assignment exists (the caller set both W and H) raises AttributeError, as the reference's `self.assigned` would.
+
+scipy.sparse data (opt-in: `mdl.accept_sparse = True`, the switch NMF, CUR, SVD and GREEDY have; Kmeans and Cmeans).  The
+reference has no sparse clustering branch; what is computed is its dense rule on toarray().  The matrix is converted once to
+canonical CSR (tocsr(), duplicates summed, indices sorted, float32 values, stored zeros kept; the caller's matrix is left
+alone) and stays sparse on the device: the H step sweeps the samples' stored entries (k_cluster_csr_assign), the W step the
+data rows' (k_cluster_csr_num); no dense image exists on host or device.  factorize(), update_w(), update_h(),
+frobenius_norm(), init_w() and init_h() work; W is a dense ndarray (Kmeans.init_w binds data[:, sorted(sel)].toarray()), H a
+dense float64 ndarray, `assigned` intp, ferr filled (compute_err=True works; NMF's -123456 sentinel is only returned without
+factors).  ferr is sqrt(sum min d^2) right behind Kmeans' own H step and otherwise the float64 identity
+||data||^2 - 2 <W^T data, H> + <W^T W, H H^T>, clamped at 0.  The other limits stay: resident, one rank, num_bases <= 128.
 """
 import random
 
@@ -19,6 +29,7 @@ import numpy as np
 
 from . import _lib
 from .nmf import NMF, _is_sparse
+from .svd import canonical_csr
 
 __all__ = ["Kmeans"]
 
@@ -27,10 +38,21 @@ class _Clustering(NMF):
     """What Kmeans and Cmeans share: the refusals, and H rebound as a new float64 array by every H step (kmeans.py:78,
     cmeans.py:81) while W is updated in place (kmeans.py:87, cmeans.py:86)."""
     _MAX_BASES = 128
+    accept_sparse = False     # opt-in, per object: scipy.sparse data stays sparse on the device (module docstring)
+
+    def _sparse_run(self):
+        """`data` is a scipy.sparse matrix and this object takes it (accept_sparse)."""
+        return bool(self.accept_sparse) and _is_sparse(self.data)
+
+    def _upload_sparse(self, ctx):
+        self._check_supported()
+        csr = canonical_csr(self.data)
+        self._warn_if_float64(csr.data)
+        ctx.set_v_csr(csr.indptr.astype(np.int64), csr.indices.astype(np.int32), csr.data.astype(np.float32))
 
     def _check_supported(self):
         name = type(self).__name__
-        if _is_sparse(self.data):
+        if _is_sparse(self.data) and not self._sparse_run():
             raise TypeError("%s: scipy.sparse data is not supported (dense data only)" % name)
         if self.stream_rows or self._stream_rows():
             raise ValueError("%s: streamed data (stream_rows) is not supported: the pass over column panels needs the data "
@@ -55,6 +77,10 @@ class _Clustering(NMF):
 
     def frobenius_norm(self):
         self._check_supported()
+        if self._sparse_run():                                 # (NMF's returns the reference's -123456 sentinel on sparse data)
+            if not (self._has('H') and self._has('W')):
+                return -123456
+            return self._sync_to_device().frobenius()
         return NMF.frobenius_norm(self)
 
     def factorize(self, niter=1, show_progress=False, compute_w=True, compute_h=True, compute_err=True):
@@ -105,7 +131,10 @@ class Kmeans(_Clustering):
     def init_w(self):                                          # kmeans.py:67-72
         self._check_supported()
         sel = random.sample(range(self._num_samples), self._num_bases)
-        self.W = np.asarray(self.data[:, np.sort(sel)])
+        if self._sparse_run():                                 # a dense W: the centres do not stay sparse
+            self.W = np.asarray(self.data.tocsc()[:, np.sort(sel)].toarray())
+        else:
+            self.W = np.asarray(self.data[:, np.sort(sel)])
 
     def init_h(self):                                          # kmeans.py:62-65
         self.H = np.zeros((self._num_bases, self._num_samples))
