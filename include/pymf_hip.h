@@ -400,6 +400,25 @@ int pmf_sivm_select(pmf_ctx* ctx, int32_t transposed, int32_t nsel, int32_t metr
 int pmf_aa_get_beta(pmf_ctx* ctx, double* beta);
 int pmf_aa_rounds(pmf_ctx* ctx, int32_t* rounds);
 
+/* CHNMF (pymf/chnmf.py; on an AA context with dense resident data, one rank): the columns on the convex hulls of pairwise random
+ * projections, chnmf.py:154-183.
+ * pmf_chnmf_hull: R is the projection matrix, base_sel x data_dimension float64, row-major, 2 <= base_sel <= min(16,
+ *   data_dimension).  proj = R V is formed in float64 on the device (float64 MFMA, V widened on load) and stays there; for every
+ *   pair of its rows (itertools.combinations order) a filter over all samples (extremes in 32 fixed directions, then every point
+ *   inside their polygon by more than 64 2^-53 times the largest coordinate is discarded) and the exact hull of the survivors
+ *   (sorted by (x, y, index); monotone chain with a strict turn test; of bit-identical points the lowest index) run back to back
+ *   without a host round trip between pairs.  A pair with more than 4096 survivors is run again with 128 directions and, if that
+ *   does not help, its hull is formed on the host from its two rows of proj: never truncated.  idx_out receives the union of all
+ *   pairs' vertices, ascending (np.unique); *count_out their number; more than cap of them is PMF_EINVAL (*count_out is set).
+ *   Every comparison that decides membership is float64; two runs give the same bits.
+ * pmf_chnmf_set_limits [test reference]: the survivor capacity (0: 4096) and the largest number of workgroups of the sweeps
+ *   (0: 1024; fewer make a workgroup own more 64-column panels) of the following pmf_chnmf_hull calls.
+ * pmf_chnmf_routes: routes[0..2] = the pairs of the last pmf_chnmf_hull that ended on the 32-direction filter, on the
+ *   128-direction rerun, on the host. */
+int pmf_chnmf_hull(pmf_ctx* ctx, const double* R, int32_t base_sel, int32_t* idx_out, int64_t cap, int64_t* count_out);
+int pmf_chnmf_set_limits(pmf_ctx* ctx, int32_t survivor_cap, int32_t max_wgs);
+int pmf_chnmf_routes(pmf_ctx* ctx, int32_t* routes);
+
 /* PCA / SVD (algo 12; pymf/svd.py:110-158 for dense data, pymf/pca.py): the SVD of the resident V through the eigen-decomposition
  * of its Gram matrix on the short side -- V^T V for rows > cols (_left_svd), V V^T otherwise (_right_svd) -- formed in float64
  * on the float64 MFMA (k_prod_f64, upper block triangle), decomposed by the float64 Jacobi solver of pmf_nndsvd_init.  Eigenvalues <= 1e-8 are dropped

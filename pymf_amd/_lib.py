@@ -81,6 +81,9 @@ SYMBOLS = [
     ("pmf_sivm_select", _c.c_int, [_ctx, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p]),
     ("pmf_aa_get_beta", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_aa_rounds", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
+    ("pmf_chnmf_hull", _c.c_int, [_ctx, _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int64, _c.POINTER(_c.c_int64)]),
+    ("pmf_chnmf_set_limits", _c.c_int, [_ctx, _c.c_int32, _c.c_int32]),
+    ("pmf_chnmf_routes", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_svd_decompose", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_svd_rank", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_svd_get", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
@@ -500,6 +503,26 @@ class Context(object):
         r = ctypes.c_int32(0)
         self._chk(self._lib.pmf_aa_rounds(self._h, ctypes.byref(r)))
         return int(r.value)
+
+    def chnmf_hull(self, R):
+        """CHNMF: the ascending indices (int32) of the columns on the convex hulls of the pairwise projections by R, base_sel x
+        data_dimension float64 (pmf_chnmf_hull); the context's data must be resident."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        assert R.ndim == 2 and R.shape[1] == self.m, (R.shape, self.m)
+        out = np.empty(self.n, dtype=np.int32)
+        cnt = ctypes.c_int64(0)
+        self._chk(self._lib.pmf_chnmf_hull(self._h, R.ctypes.data, int(R.shape[0]), out.ctypes.data, int(out.shape[0]), ctypes.byref(cnt)))
+        return out[:int(cnt.value)].copy()
+
+    def chnmf_set_limits(self, survivor_cap=0, max_wgs=0):
+        """CHNMF: survivor capacity of the exact-hull kernel and workgroup cap of the sweeps, 0 = the build's (pmf_chnmf_set_limits)."""
+        self._chk(self._lib.pmf_chnmf_set_limits(self._h, int(survivor_cap), int(max_wgs)))
+
+    def chnmf_routes(self):
+        """CHNMF: pairs of the last chnmf_hull by route: (32-direction filter, 128-direction rerun, host) (pmf_chnmf_routes)."""
+        out = np.zeros(3, dtype=np.int32)
+        self._chk(self._lib.pmf_chnmf_routes(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
 
     def svd_decompose(self):
         """PCA / SVD: decompose the resident V (pmf_svd_decompose); returns the number of singular triples kept."""

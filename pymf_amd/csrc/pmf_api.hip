@@ -44,6 +44,7 @@
 #include "pmf_sgreedy.h"
 #include "pmf_gsat.h"
 #include "pmf_aa.h"
+#include "pmf_chnmf.h"
 #include "pmf_svd.h"
 #include "pmf_cur.h"
 #include "pmf_cur_csr.h"
@@ -73,6 +74,7 @@
 #include "pmf_host_sgreedy.h"
 #include "pmf_host_gsat.h"
 #include "pmf_host_aa.h"
+#include "pmf_host_chnmf.h"
 #include "pmf_host_svd.h"
 #include "pmf_host_cur_csr.h"
 #include "pmf_host_svd_csr.h"
@@ -668,6 +670,32 @@ int pmf_aa_rounds(pmf_ctx* c, int32_t* rounds) {
   if (!c || !rounds) return fail(c, PMF_EINVAL, "pmf_aa_rounds: bad arguments");
   if (c->algo != PMF_ALGO_AA) return fail(c, PMF_EINVAL, "pmf_aa_rounds: AA only");
   *rounds = c->aa_rounds;
+  return PMF_OK;
+}
+
+int pmf_chnmf_hull(pmf_ctx* c, const double* R, int32_t base_sel, int32_t* idx_out, int64_t cap, int64_t* count_out) {
+  if (!c || !R || !count_out || cap < 0 || (cap > 0 && !idx_out)) return fail(c, PMF_EINVAL, "pmf_chnmf_hull: bad arguments");
+  if (c->algo != PMF_ALGO_AA) return fail(c, PMF_EINVAL, "pmf_chnmf_hull: AA contexts only");
+  if (base_sel < 2 || base_sel > PMF_CH_MAX_SEL || base_sel > c->m) return fail(c, PMF_EINVAL, "pmf_chnmf_hull: 2 <= base_sel <= min(16, data_dimension)");
+  PMFCHK(need(c, true, false, false));
+  if (c->v_csr || !c->dV) return fail(c, PMF_EINVAL, "pmf_chnmf_hull: dense resident data only");
+  if (multi_rank(c)) return fail(c, PMF_EINVAL, "pmf_chnmf_hull: one rank only in this build");
+  return chnmf_hull(c, R, base_sel, idx_out, cap, count_out);
+}
+
+int pmf_chnmf_set_limits(pmf_ctx* c, int32_t survivor_cap, int32_t max_wgs) {
+  if (!c) return PMF_EINVAL;
+  if (c->algo != PMF_ALGO_AA) return fail(c, PMF_EINVAL, "pmf_chnmf_set_limits: AA contexts only");
+  if (survivor_cap < 0 || survivor_cap > PMF_CH_CAP || max_wgs < 0 || max_wgs > PMF_CL_MAX_WGS)
+    return fail(c, PMF_EINVAL, "pmf_chnmf_set_limits: 0 (the build's) <= survivor_cap <= 4096, 0 (the build's) <= max_wgs <= 1024");
+  c->ch_cap = survivor_cap; c->ch_max_wgs = max_wgs;
+  return PMF_OK;
+}
+
+int pmf_chnmf_routes(pmf_ctx* c, int32_t* routes) {
+  if (!c || !routes) return fail(c, PMF_EINVAL, "pmf_chnmf_routes: bad arguments");
+  if (c->algo != PMF_ALGO_AA) return fail(c, PMF_EINVAL, "pmf_chnmf_routes: AA contexts only");
+  for (int r = 0; r < 3; ++r) routes[r] = c->ch_routes[r];
   return PMF_OK;
 }
 

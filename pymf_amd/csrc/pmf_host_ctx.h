@@ -216,6 +216,14 @@ struct pmf_ctx {
   double *dAaGram = nullptr, *dAaLam = nullptr, *dAaGinv = nullptr, *dAaBeta = nullptr;
   int aa_rounds = 0;            // rounds the last W step took
   bool aa_have_beta = false;    // dAaBeta holds the weights of a W step
+  // CHNMF (pmf_chnmf.h, on an AA context): R [16][mp] and proj = R V [16][np] in float64; per pair the partials of the extremes
+  // ([wgs][128] scores and indices, [wgs] largest magnitudes), the polygon's edges, the filter's flags [np] and counts [wgs], the
+  // survivors [4096]; the survivor counts of all pairs (and, last, the size of the union); the union's mask [np] and indices [np]
+  double *dChR = nullptr, *dChProj = nullptr, *dChPscore = nullptr, *dChPmax = nullptr, *dChEdges = nullptr;
+  int *dChPidx = nullptr, *dChCounts = nullptr, *dChSurv = nullptr, *dChNsurv = nullptr, *dChIdx = nullptr;
+  unsigned char *dChKeep = nullptr, *dChMask = nullptr;
+  int ch_cap = 0, ch_max_wgs = 0;   // pmf_chnmf_set_limits: survivors k_hull_chain takes / workgroups of the sweeps (0: the build's)
+  int ch_routes[3] = {0, 0, 0};     // pairs of the last pmf_chnmf_hull by route: 32 directions, 128 directions, host
   // SVD / PCA (pmf_svd.h): the kept eigenvectors in descending order ([KP][mp] or, rows > cols, [KP][np]; float64), the singular
   // values [KP], the projected side in float32 (V [KP][np] or, rows > cols, U [mp][KP])
   double *dSvdE = nullptr, *dSvdS = nullptr;
