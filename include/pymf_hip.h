@@ -46,6 +46,7 @@
  *   pmf_cur_ferr          CUR.frobenius_norm on sparse data  pymf/svd.py:92-107
  *   pmf_cur_leverage      CURSL.sample_probability     pymf/cursl.py:65-91 (algo 14)
  *   pmf_greedy_select     self.select of GREEDY        pymf/greedy.py:105-158 (algo 15; GREEDYCUR.sample: pymf/greedycur.py:62-68)
+ *   pmf_vq_columns / pmf_vq_assign  vq, pdist            pymf/dist.py:107-130 (any algo with dense resident data)
  *
  * Every function returns PMF_OK (0) or a negative status and never throws;
  * pmf_last_error() gives a human-readable message for the last failure.
@@ -418,6 +419,29 @@ int pmf_aa_rounds(pmf_ctx* ctx, int32_t* rounds);
 int pmf_chnmf_hull(pmf_ctx* ctx, const double* R, int32_t base_sel, int32_t* idx_out, int64_t cap, int64_t* count_out);
 int pmf_chnmf_set_limits(pmf_ctx* ctx, int32_t survivor_cap, int32_t max_wgs);
 int pmf_chnmf_routes(pmf_ctx* ctx, int32_t* routes);
+
+/* vq / pdist (pymf/dist.py:107-130) against the resident data: nq <= 128 query vectors of dimension data_dimension are measured
+ * against EVERY data column in one sweep over V (k_vq_pass, pmf_vq.h).  Q is data_dimension x nq float32 on the host, query j's
+ * component r at Q[r*ldq + j].  metric 0 'l2' = sqrtf(sum (v - q)^2), 1 'l1' = sum |v - q|, in fp32 from the difference, one
+ * running sum per pair down the rows (dist.py:61, dist.py:33: no norm expansion, so data far from the origin lose nothing);
+ * relative error of a distance at most (data_dimension + 4) 2^-24.
+ * pmf_vq_columns: idx_out[j] = the data column nearest to query j, the lowest column among equally near ones (np.argmin);
+ *   dist_out[j] (may be NULL) its distance.  A NaN distance never wins; a query whose distances are all NaN gets column 0 and
+ *   the distance NaN.  Per workgroup and query one (distance, column) partial, reduced by k_vq_close: no float atomics.
+ * pmf_vq_assign: idx_out[c] (num_samples entries; may be NULL) = the query nearest to data column c, the lowest query among
+ *   equally near ones; dist_all (may be NULL; not both) = the whole block, nq x num_samples float64 row-major, dist_all[j*n + c]
+ *   the fp32 distance of query j to column c, widened.  The block is written once by the sweep (a temporary of
+ *   8 nq num_samples bytes on the device) and read once by k_vq_argmin_rows.
+ * Both work on a context of ANY algo whose float32 V is resident and dense (pmf_set_v_dense_*, pmf_fill_v_uniform), one rank;
+ * they read V only: factors, selections and caches stay as they are (like every entry they end the float64-H bookkeeping of the
+ * previous call, as need() does).  The sweep parallelises over COLUMNS only -- one workgroup per 64-column panel at most -- so tall,
+ * narrow data (a million rows by a few hundred columns) is correct but occupies few compute units.  PMF_EINVAL, with a
+ * message, when the context holds CSR or CSC data, when no dense data is resident (streamed data never is), when nq < 1 or
+ * nq > 128, when the metric is not 0 or 1.  Two calls give the same bits.
+ * pmf_set_option "profile_vq" (0 default: the context's own kernel, 1: k_vq_pass, 2: k_vq_argmin_rows) chooses the launch that
+ * pmf_profile_enable times, on any context. */
+int pmf_vq_columns(pmf_ctx* ctx, const float* Q, int64_t ldq, int32_t nq, int32_t metric, int32_t* idx_out, double* dist_out);
+int pmf_vq_assign(pmf_ctx* ctx, const float* Q, int64_t ldq, int32_t nq, int32_t metric, int32_t* idx_out, double* dist_all);
 
 /* PCA / SVD (algo 12; pymf/svd.py:110-158 for dense data, pymf/pca.py): the SVD of the resident V through the eigen-decomposition
  * of its Gram matrix on the short side -- V^T V for rows > cols (_left_svd), V V^T otherwise (_right_svd) -- formed in float64

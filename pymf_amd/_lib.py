@@ -84,6 +84,8 @@ SYMBOLS = [
     ("pmf_chnmf_hull", _c.c_int, [_ctx, _c.c_void_p, _c.c_int32, _c.c_void_p, _c.c_int64, _c.POINTER(_c.c_int64)]),
     ("pmf_chnmf_set_limits", _c.c_int, [_ctx, _c.c_int32, _c.c_int32]),
     ("pmf_chnmf_routes", _c.c_int, [_ctx, _c.c_void_p]),
+    ("pmf_vq_columns", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_void_p]),
+    ("pmf_vq_assign", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_void_p]),
     ("pmf_svd_decompose", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_svd_rank", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_svd_get", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
@@ -523,6 +525,32 @@ class Context(object):
         out = np.zeros(3, dtype=np.int32)
         self._chk(self._lib.pmf_chnmf_routes(self._h, out.ctypes.data))
         return tuple(int(v) for v in out)
+
+    def vq_columns(self, Q, metric=0, want_dist=True):
+        """The data column nearest to each column of Q (data_dimension x nq <= 128, float32; metric 0 l2, 1 l1), lowest
+        column on ties: (int32 indices [nq], float64 distances [nq] or None) (pmf_vq_columns).  Any context with dense
+        resident data."""
+        Q = _f32c(Q)
+        assert Q.ndim == 2 and Q.shape[0] == self.m, (Q.shape, self.m)
+        nq = int(Q.shape[1])
+        idx = np.empty(max(nq, 1), dtype=np.int32)
+        dist = np.empty(max(nq, 1), dtype=np.float64) if want_dist else None
+        self._chk(self._lib.pmf_vq_columns(self._h, Q.ctypes.data, nq, nq, int(metric), idx.ctypes.data,
+                                           None if dist is None else dist.ctypes.data))
+        return idx[:nq], (None if dist is None else dist[:nq])
+
+    def vq_assign(self, Q, metric=0, want_idx=True, want_dist=False):
+        """The column of Q (data_dimension x nq <= 128, float32) nearest to each data column, lowest on ties, and / or the
+        whole nq x num_samples float64 distance block: (int32 [num_samples] or None, float64 [nq][num_samples] or None)
+        (pmf_vq_assign).  Any context with dense resident data."""
+        Q = _f32c(Q)
+        assert Q.ndim == 2 and Q.shape[0] == self.m, (Q.shape, self.m)
+        nq = int(Q.shape[1])
+        idx = np.empty(self.n, dtype=np.int32) if want_idx else None
+        dist = np.empty((max(nq, 1), self.n), dtype=np.float64) if want_dist else None
+        self._chk(self._lib.pmf_vq_assign(self._h, Q.ctypes.data, nq, nq, int(metric), None if idx is None else idx.ctypes.data,
+                                          None if dist is None else dist.ctypes.data))
+        return idx, (None if dist is None else dist[:nq])
 
     def svd_decompose(self):
         """PCA / SVD: decompose the resident V (pmf_svd_decompose); returns the number of singular triples kept."""

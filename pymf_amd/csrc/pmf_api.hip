@@ -45,6 +45,7 @@
 #include "pmf_gsat.h"
 #include "pmf_aa.h"
 #include "pmf_chnmf.h"
+#include "pmf_vq.h"
 #include "pmf_svd.h"
 #include "pmf_cur.h"
 #include "pmf_cur_csr.h"
@@ -75,6 +76,7 @@
 #include "pmf_host_gsat.h"
 #include "pmf_host_aa.h"
 #include "pmf_host_chnmf.h"
+#include "pmf_host_vq.h"
 #include "pmf_host_svd.h"
 #include "pmf_host_cur_csr.h"
 #include "pmf_host_svd_csr.h"
@@ -697,6 +699,26 @@ int pmf_chnmf_routes(pmf_ctx* c, int32_t* routes) {
   if (c->algo != PMF_ALGO_AA) return fail(c, PMF_EINVAL, "pmf_chnmf_routes: AA contexts only");
   for (int r = 0; r < 3; ++r) routes[r] = c->ch_routes[r];
   return PMF_OK;
+}
+
+int pmf_vq_columns(pmf_ctx* c, const float* Q, int64_t ldq, int32_t nq, int32_t metric, int32_t* idx_out, double* dist_out) {
+  if (!c) return PMF_EINVAL;
+  c->hd_synced = false; c->psd_fresh = false;          // (a new API call, as need() notes it; the refusals come before the device is touched)
+  PMFCHK(vq_check(c, "pmf_vq_columns", Q, ldq, nq, metric));
+  if (!idx_out) return fail(c, PMF_EINVAL, "pmf_vq_columns: idx_out is NULL");
+  if (multi_rank(c)) return fail(c, PMF_EINVAL, "pmf_vq_columns: one rank only in this build");
+  HIPCHK(c, hipSetDevice(c->device));
+  return vq_columns(c, Q, ldq, nq, metric, idx_out, dist_out);
+}
+
+int pmf_vq_assign(pmf_ctx* c, const float* Q, int64_t ldq, int32_t nq, int32_t metric, int32_t* idx_out, double* dist_all) {
+  if (!c) return PMF_EINVAL;
+  c->hd_synced = false; c->psd_fresh = false;
+  PMFCHK(vq_check(c, "pmf_vq_assign", Q, ldq, nq, metric));
+  if (!idx_out && !dist_all) return fail(c, PMF_EINVAL, "pmf_vq_assign: idx_out and dist_all are both NULL");
+  if (multi_rank(c)) return fail(c, PMF_EINVAL, "pmf_vq_assign: one rank only in this build");
+  HIPCHK(c, hipSetDevice(c->device));
+  return vq_assign(c, Q, ldq, nq, metric, idx_out, dist_all);
 }
 
 int pmf_svd_decompose(pmf_ctx* c, int32_t* rank) {
@@ -1399,6 +1421,12 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
     if (c->algo != PMF_ALGO_CUR) return fail(c, PMF_EINVAL, "profile_cur: CUR / CMD contexts only");
     if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "profile_cur: 0 (the cross product), 1 (k_lev_f64) or 2 (k_cur_sqnorms)");
     c->opt_profile_cur = (int)value;
+    choose_stat_site(c, false);
+    return PMF_OK;
+  }
+  if (std::strcmp(name, "profile_vq") == 0) {
+    if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "profile_vq: 0 (the context's own kernel), 1 (k_vq_pass) or 2 (k_vq_argmin_rows)");
+    c->opt_profile_vq = (int)value;
     choose_stat_site(c, false);
     return PMF_OK;
   }

@@ -171,13 +171,31 @@ __device__ __forceinline__ f32x4 colsweep_dist(const f32x4 st, const f32x4 nt, c
   return dist;
 }
 
+// this workgroup's panel range: its first column and its number of quads (>= 16: a workgroup owns at least one panel)
+__device__ __forceinline__ void colsweep_quad_range(const ColsweepArgs& a, int* c_begin, int* nquads) {
+  *c_begin = blockIdx.x * a.panels_per_wg * 64;
+  const int c_end = min((blockIdx.x + 1) * a.panels_per_wg, a.npanels) * 64;
+  *nquads = (c_end - *c_begin) / 4;
+}
+
 // f(c) for the first column c of every quad of this workgroup's panel range (f: a lambda, inlined)
 template <class F>
 __device__ __forceinline__ void colsweep_quads(const ColsweepArgs& a, F f) {
-  const int c_begin = blockIdx.x * a.panels_per_wg * 64;
-  const int c_end = min((blockIdx.x + 1) * a.panels_per_wg, a.npanels) * 64;
-  const int nquads = (c_end - c_begin) / 4;
+  int c_begin, nquads;
+  colsweep_quad_range(a, &c_begin, &nquads);
   for (int q = threadIdx.x; q < nquads; q += 256) f(c_begin + 4 * q);
+}
+
+// the same with uniform trips, for a body that holds barriers: f(c, live) runs in every lane of the workgroup the same number
+// of times; a lane beyond the last quad gets the last quad again with live = false (it may read, and must offer and write nothing)
+template <class F>
+__device__ __forceinline__ void colsweep_quads_uniform(const ColsweepArgs& a, F f) {
+  int c_begin, nquads;
+  colsweep_quad_range(a, &c_begin, &nquads);
+  for (int qb = 0; qb < nquads; qb += 256) {
+    const int q = qb + (int)threadIdx.x;
+    f(c_begin + 4 * min(q, nquads - 1), q < nquads);
+  }
 }
 
 // epilogue: the workgroup's (best score, lowest column attaining it) into this launch's partials
