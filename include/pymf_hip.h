@@ -47,6 +47,7 @@
  *   pmf_cur_leverage      CURSL.sample_probability     pymf/cursl.py:65-91 (algo 14)
  *   pmf_greedy_select     self.select of GREEDY        pymf/greedy.py:105-158 (algo 15; GREEDYCUR.sample: pymf/greedycur.py:62-68)
  *   pmf_vq_columns / pmf_vq_assign  vq, pdist            pymf/dist.py:107-130 (any algo with dense resident data)
+ *   pmf_set_v_gather_f32  self.data[:, idx] of SUB     pymf/sub.py:169,181 (any algo; the source holds dense resident data)
  *
  * Every function returns PMF_OK (0) or a negative status and never throws;
  * pmf_last_error() gives a human-readable message for the last failure.
@@ -442,6 +443,26 @@ int pmf_chnmf_routes(pmf_ctx* ctx, int32_t* routes);
  * pmf_profile_enable times, on any context. */
 int pmf_vq_columns(pmf_ctx* ctx, const float* Q, int64_t ldq, int32_t nq, int32_t metric, int32_t* idx_out, double* dist_out);
 int pmf_vq_assign(pmf_ctx* ctx, const float* Q, int64_t ldq, int32_t nq, int32_t metric, int32_t* idx_out, double* dist_all);
+
+/* Column gather between contexts (SUB's sample, pymf/sub.py:169,181; k_gather_cols, pmf_gather.h): dst's dense float32 V becomes
+ * src.V[:, idx[j]] for j < nsel, filled on the device -- the data of src do not cross the host link again.
+ *   idx    nsel int64 column indices of src, in any order, repeats allowed; NULL: all columns in order (a whole copy), nsel must
+ *          then equal src's n
+ *   dst    src's m rows by nsel columns (nsel == dst's n), of ANY algo; src: any algo whose float32 V is resident and dense
+ * The copy is exact to the bit (NaN payloads, infinities, -0.0); the pad of dst's image comes out zero, as a dense upload leaves
+ * it.  Everything that follows a new V is what pmf_set_v_dense_f32 runs (the caches of the old V are dropped, ||V||^2 is enqueued,
+ * CSR / CSC data of dst is released, RNMF keeps its S): a context filled this way cannot be told from one that was given the same
+ * columns by pmf_set_v_dense_f32.  The two contexts keep their own streams, ordered by two events: what src's stream holds
+ * completes before the kernel reads, and the kernel completes before work enqueued on src afterwards runs; the call does not wait
+ * for the kernel on the host and never synchronises the device.  PMF_EINVAL with a message naming the condition (through
+ * pmf_last_error(dst)), decided on the host before any launch and leaving dst's data and derived state as they were: an index < 0
+ * or >= src's n; nsel != dst's n; different row counts; src without data; src holding CSR or CSC data or in streamed mode; src ==
+ * dst; contexts on different devices; either context in a multi-rank world.
+ * pmf_set_option(dst, "profile_gather", 1) makes k_gather_cols the launch that pmf_profile_enable times on dst (0: dst's own kernel).
+ * pmf_get_v_dense_f32: the resident dense V, m x n, into out (host, row-major, leading dimension ld >= n elements); PMF_EINVAL when
+ * no dense data is resident. */
+int pmf_set_v_gather_f32(pmf_ctx* dst, pmf_ctx* src, const int64_t* idx, int64_t nsel);
+int pmf_get_v_dense_f32(pmf_ctx* ctx, float* out, int64_t ld);
 
 /* PCA / SVD (algo 12; pymf/svd.py:110-158 for dense data, pymf/pca.py): the SVD of the resident V through the eigen-decomposition
  * of its Gram matrix on the short side -- V^T V for rows > cols (_left_svd), V V^T otherwise (_right_svd) -- formed in float64

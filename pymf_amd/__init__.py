@@ -31,6 +31,7 @@ from .chnmf import CHNMF      # noqa: F401  
 from . import dist            # noqa: F401
 from . import distance        # noqa: F401  
 from .distance import vq, pdist   # noqa: F401
+from .sub import SUB          # noqa: F401  
 
-__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "SVD", "PCA", "CUR", "CMD", "CURSL", "GREEDY", "GREEDYCUR", "SIVM_CUR", "LAESA", "GMAP", "SIVM_SGREEDY", "SIVM_GSAT", "CHNMF", "pinv", "dist", "distance", "vq", "pdist"]
+__all__ = ["NMF", "NMFALS", "SNMF", "NMFNNLS", "BNMF", "NNDSVD", "CNMF", "Kmeans", "Cmeans", "SIVM", "AA", "SVD", "PCA", "CUR", "CMD", "CURSL", "GREEDY", "GREEDYCUR", "SIVM_CUR", "LAESA", "GMAP", "SIVM_SGREEDY", "SIVM_GSAT", "CHNMF", "SUB", "pinv", "dist", "distance", "vq", "pdist"]
 __version__ = "0.1.0"

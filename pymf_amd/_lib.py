@@ -86,6 +86,8 @@ SYMBOLS = [
     ("pmf_chnmf_routes", _c.c_int, [_ctx, _c.c_void_p]),
     ("pmf_vq_columns", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_void_p]),
     ("pmf_vq_assign", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_void_p]),
+    ("pmf_set_v_gather_f32", _c.c_int, [_ctx, _ctx, _c.c_void_p, _c.c_int64]),
+    ("pmf_get_v_dense_f32", _c.c_int, [_ctx, _c.c_void_p, _c.c_int64]),
     ("pmf_svd_decompose", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_svd_rank", _c.c_int, [_ctx, _c.POINTER(_c.c_int32)]),
     ("pmf_svd_get", _c.c_int, [_ctx, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
@@ -551,6 +553,21 @@ class Context(object):
         self._chk(self._lib.pmf_vq_assign(self._h, Q.ctypes.data, nq, nq, int(metric), None if idx is None else idx.ctypes.data,
                                           None if dist is None else dist.ctypes.data))
         return idx, (None if dist is None else dist[:nq])
+
+    def set_v_gather(self, src, idx=None):
+        """This context's dense V <- src's resident V[:, idx] on the device (pmf_set_v_gather_f32); idx None: all of src's
+        columns in order.  Indices may repeat and come in any order; src is a Context with dense resident data."""
+        if idx is None:
+            self._chk(self._lib.pmf_set_v_gather_f32(self._h, src._h, None, int(src.n)))
+            return
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        self._chk(self._lib.pmf_set_v_gather_f32(self._h, src._h, idx.ctypes.data if idx.size else None, int(idx.shape[0])))
+
+    def get_v_dense(self):
+        """The resident dense V, m x n float32 (pmf_get_v_dense_f32)."""
+        V = np.empty((self.m, self.n), dtype=np.float32)
+        self._chk(self._lib.pmf_get_v_dense_f32(self._h, V.ctypes.data, V.shape[1]))
+        return V
 
     def svd_decompose(self):
         """PCA / SVD: decompose the resident V (pmf_svd_decompose); returns the number of singular triples kept."""

@@ -46,6 +46,7 @@
 #include "pmf_aa.h"
 #include "pmf_chnmf.h"
 #include "pmf_vq.h"
+#include "pmf_gather.h"
 #include "pmf_svd.h"
 #include "pmf_cur.h"
 #include "pmf_cur_csr.h"
@@ -77,6 +78,7 @@
 #include "pmf_host_aa.h"
 #include "pmf_host_chnmf.h"
 #include "pmf_host_vq.h"
+#include "pmf_host_gather.h"
 #include "pmf_host_svd.h"
 #include "pmf_host_cur_csr.h"
 #include "pmf_host_svd_csr.h"
@@ -256,6 +258,7 @@ int pmf_ctx_destroy(pmf_ctx* c) {
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->w_stream) { (void)hipStreamSynchronize(c->w_stream); (void)hipStreamDestroy(c->w_stream); }
   for (hipEvent_t e : {c->ev_mt[0], c->ev_mt[1], c->ev_w[0], c->ev_w[1]}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->ev_ga) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->stat.ev) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->coll_ev) (void)hipEventDestroy(e);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -286,9 +289,9 @@ static int rnmf_data_change_end(pmf_ctx* c) {
   return PMF_OK;
 }
 
-static int set_v_dense(pmf_ctx* c, const void* V, bool f64, int64_t ld, const char* who) {
-  if (!c || !V || ld < c->n) return fail(c, PMF_EINVAL, std::string(who) + ": bad arguments");
-  HIPCHK(c, hipSetDevice(c->device));
+// A dense fill of dV in two halves around the fill itself (a host upload, pmf_fill_v_uniform, pmf_set_v_gather_f32).
+// dense_v_begin: whatever other form of the data the context held goes, dV exists, RNMF's D is S again.
+static int dense_v_begin(pmf_ctx* c) {
   PMFCHK(sivm_csc_left(c));
   PMFCHK(cur_csr_left(c));
   PMFCHK(svd_csr_left(c));
@@ -297,16 +300,48 @@ static int set_v_dense(pmf_ctx* c, const void* V, bool f64, int64_t ld, const ch
   PMFCHK(ensure_wbufs(c));
   PMFCHK(ensure_dv(c));
   PMFCHK(rnmf_data_change_begin(c));
-  PMFCHK(f64 ? upload_rows(c, c->dV, c->np, static_cast<const double*>(V), ld, c->m, c->n)
-             : upload_rows(c, c->dV, c->np, static_cast<const float*>(V), ld, c->m, c->n));
+  return PMF_OK;
+}
+// dense_v_end: everything that follows a new V, the same whoever filled it
+static int dense_v_end(pmf_ctx* c) {
   PMFCHK(rnmf_data_change_end(c));
   c->have_v = true; c->v_csr = false; c->csr_dense = false; v_replaced(c);
   nmf_csr_left(c);
   PMFCHK(local_vnorm(c));
   return PMF_OK;
 }
+
+static int set_v_dense(pmf_ctx* c, const void* V, bool f64, int64_t ld, const char* who) {
+  if (!c || !V || ld < c->n) return fail(c, PMF_EINVAL, std::string(who) + ": bad arguments");
+  HIPCHK(c, hipSetDevice(c->device));
+  PMFCHK(dense_v_begin(c));
+  PMFCHK(f64 ? upload_rows(c, c->dV, c->np, static_cast<const double*>(V), ld, c->m, c->n)
+             : upload_rows(c, c->dV, c->np, static_cast<const float*>(V), ld, c->m, c->n));
+  return dense_v_end(c);
+}
 int pmf_set_v_dense_f32(pmf_ctx* c, const float* V, int64_t ld) { return set_v_dense(c, V, false, ld, "pmf_set_v_dense_f32"); }
 int pmf_set_v_dense_f64(pmf_ctx* c, const double* V, int64_t ld) { return set_v_dense(c, V, true, ld, "pmf_set_v_dense_f64"); }
+
+int pmf_set_v_gather_f32(pmf_ctx* dst, pmf_ctx* src, const int64_t* idx, int64_t nsel) {
+  if (!dst) return fail(nullptr, PMF_EINVAL, "pmf_set_v_gather_f32: dst is NULL");
+  std::vector<int32_t> idx32;
+  PMFCHK(gather_check(dst, src, idx, nsel, &idx32));     // every refusal: dst is as it was
+  dst->hd_synced = false; dst->psd_fresh = false;        // (a new API call, as need() notes it)
+  HIPCHK(dst, hipSetDevice(dst->device));
+  PMFCHK(gather_stage_idx(dst, idx32));
+  PMFCHK(dense_v_begin(dst));
+  PMFCHK(gather_fill(dst, src, /*ident=*/idx == nullptr, nsel));
+  return dense_v_end(dst);
+}
+
+int pmf_get_v_dense_f32(pmf_ctx* c, float* out, int64_t ld) {
+  if (!c) return PMF_EINVAL;
+  c->hd_synced = false; c->psd_fresh = false;
+  if (const char* why = gather_no_dense(c)) return fail(c, PMF_EINVAL, std::string("pmf_get_v_dense_f32: the context ") + why);
+  if (!out || ld < c->n) return fail(c, PMF_EINVAL, "pmf_get_v_dense_f32: out is NULL or ld < n");
+  HIPCHK(c, hipSetDevice(c->device));
+  return download_padded(c, out, ld, c->dV, c->np, c->m, c->n);
+}
 
 int pmf_set_v_csr_f32(pmf_ctx* c, const int64_t* indptr, const int32_t* indices, const float* vals,
                       int64_t nnz) {
@@ -377,20 +412,9 @@ static int fill(pmf_ctx* c, float* X, int64_t ld, int64_t rows, int64_t cols, in
 
 int pmf_fill_v_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   if (!c) return PMF_EINVAL;
-  PMFCHK(sivm_csc_left(c));
-  PMFCHK(cur_csr_left(c));
-  PMFCHK(svd_csr_left(c));
-  PMFCHK(greedy_csr_left(c));
-  PMFCHK(cluster_csr_left(c));
-  PMFCHK(ensure_wbufs(c));
-  PMFCHK(ensure_dv(c));
-  PMFCHK(rnmf_data_change_begin(c));
+  PMFCHK(dense_v_begin(c));
   PMFCHK(fill(c, c->dV, c->np, c->m, c->n, row0, seed));
-  PMFCHK(rnmf_data_change_end(c));
-  c->have_v = true; c->v_csr = false; c->csr_dense = false; v_replaced(c);
-  nmf_csr_left(c);
-  PMFCHK(local_vnorm(c));
-  return PMF_OK;
+  return dense_v_end(c);
 }
 int pmf_fill_w_uniform(pmf_ctx* c, uint64_t seed, int64_t row0) {
   if (!c) return PMF_EINVAL;
@@ -1427,6 +1451,12 @@ int pmf_set_option(pmf_ctx* c, const char* name, int64_t value) {
   if (std::strcmp(name, "profile_vq") == 0) {
     if (value < 0 || value > 2) return fail(c, PMF_EINVAL, "profile_vq: 0 (the context's own kernel), 1 (k_vq_pass) or 2 (k_vq_argmin_rows)");
     c->opt_profile_vq = (int)value;
+    choose_stat_site(c, false);
+    return PMF_OK;
+  }
+  if (std::strcmp(name, "profile_gather") == 0) {
+    if (value < 0 || value > 1) return fail(c, PMF_EINVAL, "profile_gather: 0 (the context's own kernel) or 1 (k_gather_cols)");
+    c->opt_profile_gather = (int)value;
     choose_stat_site(c, false);
     return PMF_OK;
   }

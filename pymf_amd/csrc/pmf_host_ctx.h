@@ -11,7 +11,7 @@ std::string g_create_error;
 
 // Launch sites that can be bracketed by HIP events (pmf_profile_enable): ONE of them, the dominant
 // m-sized kernel of the path the context takes, is recorded at a time (choose_stat_site).
-enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_SIVM_ROWS, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY, SITE_CUR_LEV, SITE_CUR_SQNORMS, SITE_LAESA, SITE_GMAP, SITE_SGREEDY, SITE_VQ, SITE_VQ_ARGMIN };
+enum { SITE_NONE = 0, SITE_FUSED, SITE_ROWGEMM_W, SITE_NNQP_W, SITE_MATERIALIZE, SITE_CSR_PASS, SITE_CLUSTER, SITE_SIVM, SITE_SIVM_ROWS, SITE_AA, SITE_SVD, SITE_CUR, SITE_GREEDY, SITE_CUR_LEV, SITE_CUR_SQNORMS, SITE_LAESA, SITE_GMAP, SITE_SGREEDY, SITE_VQ, SITE_VQ_ARGMIN, SITE_GATHER };
 
 struct KernelStat {
   std::string name = "none";
@@ -248,6 +248,12 @@ struct pmf_ctx {
   bool cur_valid = false;       // they belong to the current V.  <- V
   int opt_profile_cur = 0;      // pmf_set_option("profile_cur"): pmf_profile_enable times 0 the cross product, 1 k_lev_f64, 2 k_cur_sqnorms
   int opt_profile_vq = 0;       // pmf_set_option("profile_vq"): pmf_profile_enable times 0 the context's own kernel, 1 k_vq_pass, 2 k_vq_argmin_rows (pmf_vq.h)
+  // pmf_set_v_gather_f32 (pmf_gather.h, pmf_host_gather.h), on the DESTINATION context: the index array as the kernel reads it, the
+  // events that order the source's stream against the kernel (0: the source's work before it, 1: the kernel before the source's next)
+  int32_t* dGaIdx = nullptr;
+  int64_t ga_idx_cap = 0;
+  hipEvent_t ev_ga[2] = {nullptr, nullptr};
+  int opt_profile_gather = 0;   // pmf_set_option("profile_gather"): pmf_profile_enable times k_gather_cols, on any context
   // CUR / CMD on CSR data (pmf_cur_csr.h, pmf_host_cur_csr.h): v_csr with both CSR images resident (dIndptr ..., dTIndptr ...) and no
   // dV; on the host the row pointers (the chunk count of k_cur_csr_mid follows the longest selected row), ||data||^2 as the sum
   // of the row norms in row order, and the error of the last pmf_cur_compute by the trace identity (pmf_cur_ferr)

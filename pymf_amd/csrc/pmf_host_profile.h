@@ -13,7 +13,10 @@ void choose_stat_site(pmf_ctx* c, bool gram) {
   const int old_site = st.site;
   st.site = SITE_NONE; st.name = "none"; st.flops = st.bytes = st.exec_flops = 0.0;
   char buf[96];
-  if (c->opt_profile_vq) {                                        // any context: vq_stat writes the name and the figures of the launch at hand
+  if (c->opt_profile_gather) {                                    // any context: gather_stat writes the name and the figures of the launch at hand
+    st.site = SITE_GATHER;
+    st.name = "k_gather_cols<idx>";
+  } else if (c->opt_profile_vq) {                                 // any context: vq_stat writes the name and the figures of the launch at hand
     st.site = c->opt_profile_vq == 1 ? SITE_VQ : SITE_VQ_ARGMIN;
     st.name = c->opt_profile_vq == 1 ? "k_vq_pass<l2>" : "k_vq_argmin_rows";
   } else if (c->opt_profile_sivm_rows && (c->algo == PMF_ALGO_SIVM || c->algo == PMF_ALGO_CUR)) {

@@ -298,6 +298,33 @@ class NMF(object):
         self._v_src = self.data
         self._v_fp = fp
 
+    def upload_data(self):
+        """Make `data` resident now, factors untouched: the context.  As before any step, an unchanged `data` (check_data:
+        by its digest) costs no upload.  What SUB calls on the model that holds the full data."""
+        ctx = self._context()
+        self._upload_data(ctx)
+        return ctx
+
+    def adopt_data_from(self, source, columns=None):
+        """"Your V is resident": fill this model's device V from `source`'s context -- its columns `columns` (any order,
+        repeats allowed), or all of them (None) -- on the device (pmf_set_v_gather_f32), and book it as an upload of `data`
+        would be: the counterpart of `_v_src` / `_v_fp` for a V that did not come from the host.  `data` must hold what
+        source.data[:, columns] holds (the caller's contract: SUB slices it in the same call); its digest is taken here, so
+        a later in-place edit of it is noticed as after any upload.  `source` must have its data resident and current
+        (source.upload_data() in the same call); dense data, one rank."""
+        if self._world().size > 1:
+            raise NotImplementedError("%s: adopt_data_from: one rank only" % type(self).__name__)
+        if source._ctx is None or source._v_src is not source.data or _is_sparse(source.data):
+            raise ValueError("adopt_data_from: the source model holds no dense resident data (upload_data() first)")
+        arr = np.asarray(self.data[:, :])
+        self._warn_if_float64(arr)
+        ctx = self._context()
+        ctx.set_v_gather(source._ctx, columns)
+        whole = columns is None and self.data is source.data
+        self._v_src = self.data
+        self._v_fp = None if not self.check_data else source._v_fp if whole and source._v_fp is not None else _fingerprint(arr)
+        return ctx
+
     def _warn_if_float64(self, arr):
         if getattr(arr, "dtype", None) == np.float64 and not self.__dict__.get("_warned_f64", False):
             self._warned_f64 = True
